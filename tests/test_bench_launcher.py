@@ -90,11 +90,48 @@ def test_heartbeat_reports_long_phases(capsys):
 
 def test_multi_gpu_default_is_the_metric():
     """BASELINE.json's metric is the ONE fixed 512x512x256 R=8 map at 1/2/4/8 GPUs, split by the
-    north-star K-slab layout: --gpus N defaults to strong scaling, K-slab, config c3; the other
-    layout and weak scaling ride along as extra keys."""
+    north-star K-slab layout: --gpus N defaults to strong scaling, K-slab, config c3; under --full
+    the other layout and weak scaling ride along as extra keys."""
     a = _args(["--gpus", "8"])
     assert a.scaling == "strong" and a.shard == "kslab" and a.config == "c3"
     assert not a.no_extra
+    assert not a.full and a.dump_outputs is None  # a plain run: the headline figure only
+    a = _args(["--gpus", "8", "--full", "--dump-outputs", "d"])
+    assert a.full and not a.no_extra and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 (float64 kept), per-rank names at
+    N > 1, and the same bytes from two calls."""
+    import numpy as np
+    import torch
+    S = torch.arange(24, dtype=torch.float32).reshape(2, 1, 3, 4)
+    arrays = {"S": S, "C": np.arange(6, dtype=np.float16).reshape(2, 3),
+              "nll": np.array([1.5], dtype=np.float64)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert shapes == {"S": [2, 1, 3, 4], "C": [2, 3], "nll": [1]}
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert got["S"].dtype == np.float32 and got["C"].dtype == np.float32
+    assert got["nll"].dtype == np.float64
+    assert np.array_equal(got["S"], S.numpy()) and np.array_equal(got["C"], arrays["C"])
+    bench.dump_outputs(str(tmp_path / "b"), arrays, rank=1, world=2)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "S.rank1.npy")), S.numpy())
+
+
+def test_dump_outputs_samples_past_the_size_limit(tmp_path, monkeypatch):
+    """Arrays over the byte budget are cut to a fixed seeded sample: under the budget in all,
+    small arrays whole, and the same entries every time."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    big = np.arange(10000, dtype=np.float32)
+    small = np.arange(7, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"S": big, "C": small})
+    a, b = (np.load(str(tmp_path / d / "S.npy")) for d in ("a", "b"))
+    assert np.array_equal(a, b) and 0 < a.size <= 512
+    assert np.all(np.diff(a) > 0) and np.array_equal(a, big[a.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "C.npy")), small)
+    assert a.nbytes + small.nbytes <= 4096
 
 
 def test_extra_measurement_plan(monkeypatch):

@@ -2,6 +2,8 @@
 # A/B (ENVS entries: comma-separated VAR=value sets): default build vs variant libraries (bench value, us/step, fused kernel and C-finish time),
 # alternating, REPS rounds:  REPS=3 [ENVS="QSC_FIN=0 QSC_FIN=1"] bash tools/gpu_ab.sh variants/libqsc_a.so ...
 mkdir -p gpurun_out
+# (the per-kernel times printed below are part of the --full line)
+BENCH_ARGS="--full ${BENCH_ARGS}"
 for rep in $(seq ${REPS:-3}); do
   for e in ${ENVS:-QSC_FIN=0}; do
     for lib in default "$@"; do

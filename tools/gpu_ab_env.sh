@@ -10,6 +10,8 @@ if [ -z "$SKIP_TESTS" ]; then
   faulted $G/pytest_gpu.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { grep -E "FAILED|Error" $G/pytest_gpu.log | head; exit $rc; }
 fi
+# (the per-kernel times printed below are part of the --full line)
+BENCH_ARGS="--full ${BENCH_ARGS}"
 i=0
 for rep in ${REPS:-1}; do
 for e in ${ENVS:--}; do

@@ -7,6 +7,7 @@ run() {
   timeout -k 10 300 python bench.py --cpu-baseline 0 "$@" > gpurun_out/cfg/$tag.log 2>&1 || exit $?
   tail -1 gpurun_out/cfg/$tag.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$tag', round(d['value']), 'grad-steps/s', d['config'].get('workload'), d['roofline']['frac'])"
 }
-run c2 --config c2
-run c4 --config c4
-run c4_strong --config c4 --scaling strong
+# (--full: the roofline fraction printed above is not part of a plain line)
+run c2 --full --config c2
+run c4 --full --config c4
+run c4_strong --full --config c4 --scaling strong

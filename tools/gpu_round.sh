@@ -5,6 +5,8 @@
 #   OUT=r01 [SKIP_TESTS=1] [NO_PMC=1] bash tools/gpu_round.sh
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=${OUT:-r01}
+# the whole line (kernels, roofline, CPU baseline), not only the headline figure
+BENCH_ARGS="--full ${BENCH_ARGS}"
 G=$R/gpurun_out/$OUT
 mkdir -p $G
 export TMPDIR=/tmp
