@@ -56,7 +56,7 @@ typedef struct qsc_model {
   double sigma;      /* probit noise standard deviation */
   double offset;     /* log-model offset (ignored when log_model == 0) */
   float bounds[QSC_MAX_BOUNDS]; /* bin boundaries as the caller gives them (unclamped) */
-  int32_t loss;      /* QSC_LOSS_PROBIT (0) or QSC_LOSS_SQUARED (1), see below */
+  int32_t loss;      /* QSC_LOSS_PROBIT (0), QSC_LOSS_SQUARED (1) or QSC_LOSS_LOGIT (2), see below */
   int32_t reserved_;
 } qsc_model;
 /* loss of the fused passes (qsc_spass / qsc_cpass):
@@ -65,10 +65,17 @@ typedef struct qsc_model {
  *                      (get_quantized_obs_from_ordinal, qmc/quantization_model_log.py:43-51):
  *                      the Euclidean "DowJons" criterion ||Wx (T_hat - Obs)||_F^2 of
  *                      qmc/qmc_dowjons.ipynb :142, :160 (sigma is unused).
+ *   QSC_LOSS_LOGIT:   -sum_obs log P(y | x) under the logistic (ordered-logit) link
+ *                      F(y) = 1 / (1 + exp(-y / s)), s = sigma  (F_sigmoid,
+ *                      qmc/quantization_model.py:43-47, at s = 1):
+ *                      P = F(b[y+1] - x) - F(b[y] - x) with prob_probit's edge handling (linear
+ *                      model: b[0] = -1e5, b[-1] = 1e5; log model: raw edges).  sigma is the
+ *                      logistic SCALE; the noise standard deviation is s pi / sqrt(3).
  * with x = t (linear) or log(t + offset) (log model); the state's nll_* fields then hold the
- * squared-loss sums. */
+ * squared-loss sums (QSC_LOSS_SQUARED) or the logistic NLL (QSC_LOSS_LOGIT). */
 #define QSC_LOSS_PROBIT 0
 #define QSC_LOSS_SQUARED 1
+#define QSC_LOSS_LOGIT 2
 
 /* Adam hyper-parameters (torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8).  The
  * per-step bias corrections are computed on the device from the step counters held in the
@@ -197,6 +204,19 @@ QSC_API int qsc_prob_probit_bwd(const int64_t* Y, const float* Xhat, const float
                                 const qsc_model* m, float* gX, void* stream);
 /* F_probit: qmc/quantization_model.py:57-61 */
 QSC_API int qsc_f_probit(const float* y, int64_t n, double sigma, float* out, void* stream);
+/* Logistic link (QSC_LOSS_LOGIT) counterparts of the three calls above; m->sigma / scale is the
+ * logistic scale s, m->loss is not read.
+ * F_logit: F(y) = 1 / (1 + exp(-y / s)); F_sigmoid, qmc/quantization_model.py:43-47, is s = 1.
+ * Evaluated as exp(-|y|/s) / (1 + exp(-|y|/s)) or its complement, so neither tail overflows. */
+QSC_API int qsc_f_logit(const float* y, int64_t n, double scale, float* out, void* stream);
+/* prob_logit: prob_probit (qmc/quantization_model.py:22-39, qmc/quantization_model_log.py:23-41)
+ * with F_logit in place of F_probit: P = F(b[Y+1] - Xhat) - F(b[Y] - Xhat), same edge clamps. */
+QSC_API int qsc_prob_logit(const int64_t* Y, const float* Xhat, int64_t n, const qsc_model* m,
+                           float* P, void* stream);
+/* vector-Jacobian product of prob_logit w.r.t. Xhat: gX = gP * (f(w) - f(u)) / s, f = F (1 - F),
+ * u = (b[Y+1] - Xhat) / s, w = (b[Y] - Xhat) / s  (the autograd backward of the lines above) */
+QSC_API int qsc_prob_logit_bwd(const int64_t* Y, const float* Xhat, const float* gP, int64_t n,
+                               const qsc_model* m, float* gX, void* stream);
 /* mid-bin values: get_quantized_obs_from_ordinal, qmc/quantization_model_log.py:43-51 */
 QSC_API int qsc_obs_from_ordinal(const int64_t* Y, int64_t n, const qsc_model* m, float* out,
                                  void* stream);
@@ -269,7 +289,7 @@ QSC_API int qsc_obs_layout(const uint8_t* codes, int32_t K, int32_t P, int32_t P
                            int64_t* s_off, int32_t* c_width, int64_t* c_off, int32_t* c_kmap,
                            void* ws, size_t ws_bytes, qsc_obs_desc* desc, void* stream);
 /* 1 if the signed-row entry format (rowfmt = 1) applies to this layout at rank R under model m:
- * the one-bit linear model (saturated outer edges, probit loss), narrow entries, and the doubled
+ * the one-bit linear model (saturated outer edges, probit or logistic loss), narrow entries, and the doubled
  * LDS tables of every pass fit.  Passes given a rowfmt = 1 layout they cannot run return
  * QSC_EINVAL. */
 QSC_API int qsc_obs_signed_rows_ok(const qsc_obs_desc* desc, int32_t R, const qsc_model* m);
@@ -305,6 +325,7 @@ QSC_API int qsc_perm_scatter(const float* pos, const int32_t* perm, int32_t R, i
  *   per observed entry e=(k,p):  t = sum_r S[r,p] C[r,k]  (reference order),
  *   x = t (linear) or log(t + offset), P = prob_probit, nll -= log P,
  *   g = (exp(-u^2) - exp(-w^2)) / (a sqrt(pi) P) * (log ? 1/(t+offset) : 1)
+ *   (QSC_LOSS_LOGIT: P = prob_logit, g = (f(u) - f(w)) / (s P) * (log ? 1/(t+offset) : 1))
  *   dS[r,p] = sum_k g C[r,k], dC[r,k] = sum_p g S[r,p]
  *   (replaces get_tensor -> log -> prob_probit -> -sum(Wx log P) -> autograd backward,
  *    qmc/qmc.ipynb :566-575 and :626-633)

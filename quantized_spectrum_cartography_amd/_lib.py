@@ -21,7 +21,7 @@ QSC_SLICE = 32  # S-format slice (pixel positions per list group), include/qsc.h
 QSC_ENTRY_TAIL = 256  # pad entries after the last list (read-ahead tail), include/qsc.h
 QSC_EINVAL = 100000
 QSC_EUNSUPPORTED = 100001
-LOSSES = {"probit": 0, "squared": 1}  # QSC_LOSS_PROBIT, QSC_LOSS_SQUARED
+LOSSES = {"probit": 0, "squared": 1, "logit": 2}  # QSC_LOSS_PROBIT, _SQUARED, _LOGIT
 UNOBSERVED = 0xFF
 
 

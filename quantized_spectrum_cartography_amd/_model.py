@@ -117,6 +117,85 @@ def F_probit(y, std):
     return out.to(y.device)
 
 
+# ---------------------------------------------------------------------------------------
+# logistic (ordered-logit) link: F_logit, prob_logit (autograd w.r.t. X_hat), quantize_logit
+# ---------------------------------------------------------------------------------------
+def F_logit(y, scale=1.0):
+    """1 / (1 + exp(-y / scale)): the reference's F_sigmoid (qmc/quantization_model.py:43-47) with
+    a scale, on the HIP op qsc_f_logit (stable in both tails).  The logistic noise it is the CDF
+    of has standard deviation scale * pi / sqrt(3)."""
+    yd = _dev(y.to(_F32))
+    out = torch.empty_like(yd)
+    _lib.call("qsc_f_logit", _lib.ptr(yd), yd.numel(), float(scale), _lib.ptr(out), _lib.stream())
+    return out.to(y.device)
+
+
+class _ProbLogit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Y, X_hat, model):
+        Yd, Xd = _dev(Y.to(torch.int64)), _dev(X_hat.to(_F32))
+        Yd, Xd = torch.broadcast_tensors(Yd, Xd)
+        Yd, Xd = Yd.contiguous(), Xd.contiguous()
+        P = torch.empty(Xd.shape, dtype=_F32, device=Xd.device)
+        _lib.call("qsc_prob_logit", _lib.ptr(Yd), _lib.ptr(Xd), Xd.numel(), model, _lib.ptr(P),
+                  _lib.stream())
+        ctx.model = model
+        ctx.save_for_backward(Yd, Xd)
+        ctx.x_shape = X_hat.shape
+        return P
+
+    @staticmethod
+    def backward(ctx, gP):
+        Yd, Xd = ctx.saved_tensors
+        gP = gP.to(_F32).contiguous()
+        gX = torch.empty_like(Xd)
+        _lib.call("qsc_prob_logit_bwd", _lib.ptr(Yd), _lib.ptr(Xd), _lib.ptr(gP), Xd.numel(),
+                  ctx.model, _lib.ptr(gX), _lib.stream())
+        if gX.shape != ctx.x_shape:
+            gX = gX.sum_to_size(ctx.x_shape)
+        return None, gX, None
+
+
+def prob_logit(Y, X_hat, bin_boundaries, scale, log_model=False):
+    """P(Y | X_hat) = F(b[Y+1] - X_hat) - F(b[Y] - X_hat), F = F_logit(., scale).
+
+    prob_probit (qmc/quantization_model.py:22-39, qmc/quantization_model_log.py:23-41) with the
+    logistic link in place of the probit one, the same edge handling (linear: b[0], b[-1]
+    clamped to -/+1e5; log model: raw edges).  `scale` is the logistic scale s (noise standard
+    deviation s * pi / sqrt(3)); X_hat is in the model domain, as for prob_probit.
+    """
+    model = _lib.make_model(bin_boundaries, scale, 0.0, log_model, loss="logit")
+    out_dev = X_hat.device
+    P = _ProbLogit.apply(Y, X_hat, model)
+    return P if out_dev.type == "cuda" else P.to(out_dev)
+
+
+def quantize_logit(X, scale, bin_boundaries, offset=None, log_model=False, noise=None):
+    """Bin index of X + scale * L (linear) or log(X + offset) + scale * L (log model), L standard
+    logistic noise: quantize (qmc/quantization_model.py:8-20, _log.py:9-21) under the logistic
+    link.  L is drawn on the host as log(u) - log1p(-u), u = torch.rand(X.shape) from torch's
+    global CPU generator (pass `noise` to supply L explicitly); the observation is formed on the
+    host and binned on the GPU (qsc_bin_codes)."""
+    out_dev = X.device
+    if log_model:
+        from .utils import LOG_OFFSET_7_ADJUSTED
+        offset = LOG_OFFSET_7_ADJUSTED if offset is None else float(offset)
+        if not offset > 0.0:
+            raise ValueError("the log model needs offset > 0 (log(X + offset) at X = 0)")
+    if noise is None:
+        u = torch.rand(X.shape)
+        noise = torch.log(u) - torch.log1p(-u)
+    base = X.detach().cpu().to(_F32)
+    if log_model:
+        base = torch.log(base + offset)
+    xd = _dev(base + noise.cpu().to(_F32) * scale)
+    m = _lib.make_model(bin_boundaries, scale, offset if log_model else 0.0, log_model,
+                        loss="logit")
+    Y = torch.empty(xd.shape, dtype=torch.int64, device=xd.device)
+    _lib.call("qsc_bin_codes", _lib.ptr(xd), xd.numel(), m, _lib.ptr(Y), _lib.stream())
+    return Y.to(out_dev)
+
+
 def F_sigmoid(y):
     """1/(1+exp(-y)) (qmc/quantization_model.py:41-45)."""
     return torch.sigmoid(y)

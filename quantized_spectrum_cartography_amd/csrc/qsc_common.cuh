@@ -256,6 +256,18 @@ inline Lik make_lik(const qsc_model* m) {
 #if QSC_FTZ_SAT
   l.ob_kg = (float)((double)p.kgrad / kMillsK * 0x1p101);  // E is carried 2^-101 low
 #endif
+  if (m->loss == QSC_LOSS_LOGIT) {
+    // logistic link F(y) = 1 / (1 + exp(-y / s)), s = sigma: the general kinds divide by a = s,
+    // the one-bit kinds carry z~ = log2(e) (thr - t) / s and scale |g| = (1 - P) / s
+    l.a = (float)m->sigma;
+    l.inv_a = 1.0f / l.a;
+    l.kgrad = l.inv_a;
+    l.thr_a = (float)((double)l.thr / (double)l.a);
+    const double l2e = 1.4426950408889634;
+    l.ob_scale = (float)(l2e / (double)l.a);
+    l.ob_thr = (float)((double)l.thr * l2e / (double)l.a);
+    l.ob_kg = l.inv_a;
+  }
   return l;
 }
 
@@ -265,10 +277,39 @@ inline Lik make_lik(const qsc_model* m) {
 // LIK_ONEBIT_SR: the one-bit kind on signed-row layouts (qsc_obs_desc::rowfmt 1): the gathered
 // row carries the entry's sign and threshold, [s*row, s*thr'] (s = +1 for code 0, -1 for code 1,
 // pad rows [0, kPadZ]), so the walk evaluates z~ = s*z' with no code, pad or sign handling.
-enum { LIK_ONEBIT = 0, LIK_GENERAL = 1, LIK_SQUARED = 2, LIK_ONEBIT_SR = 3 };
+// LIK_LOGIT_*: the same three forms under the logistic link (QSC_LOSS_LOGIT, logit_* below).
+enum {
+  LIK_ONEBIT = 0,
+  LIK_GENERAL = 1,
+  LIK_SQUARED = 2,
+  LIK_ONEBIT_SR = 3,
+  LIK_LOGIT_ONEBIT = 4,
+  LIK_LOGIT_GENERAL = 5,
+  LIK_LOGIT_ONEBIT_SR = 6
+};
+// kinds whose entries are signed rows / whose rows are scaled for the one-bit z~
+constexpr bool is_sr(int kind) { return kind == LIK_ONEBIT_SR || kind == LIK_LOGIT_ONEBIT_SR; }
+constexpr bool is_onebit_cf(int kind) { return kind == LIK_ONEBIT || kind == LIK_LOGIT_ONEBIT; }
+constexpr bool is_logit(int kind) {
+  return kind == LIK_LOGIT_ONEBIT || kind == LIK_LOGIT_GENERAL || kind == LIK_LOGIT_ONEBIT_SR;
+}
+// the signed-row form of a one-bit kind
+constexpr int sr_kind_of(int kind) {
+  return kind == LIK_LOGIT_ONEBIT ? LIK_LOGIT_ONEBIT_SR : LIK_ONEBIT_SR;
+}
+
+// Logistic link: the +-1e5 clamp edges of the linear model saturate (F exactly 0 or 1 in fp32:
+// exp overflows beyond |y| / s = 88.73) whenever 1e5 / s stays beyond that; s < 1e3 keeps the
+// margin for every x of interest (|x| < 1e4).  Decided as make_probit decides lo_sat / hi_sat.
+inline bool logit_sat(const qsc_model* m) {
+  return m->log_model == 0 && (float)m->sigma < 1.0e3f;
+}
 
 inline int lik_kind(const qsc_model* m) {
   if (m->loss == QSC_LOSS_SQUARED) return LIK_SQUARED;
+  if (m->loss == QSC_LOSS_LOGIT)
+    return (m->log_model == 0 && m->nbounds == 3 && logit_sat(m)) ? LIK_LOGIT_ONEBIT
+                                                                  : LIK_LOGIT_GENERAL;
   const Probit p = make_probit(m);
   return (m->log_model == 0 && m->nbounds == 3 && p.lo_sat && p.hi_sat) ? LIK_ONEBIT : LIK_GENERAL;
 }
@@ -362,6 +403,35 @@ __device__ __forceinline__ void onebit_sr_pg(f2v z, const Lik& c, f2v& P, f2v& g
   g = (E * splat2(c.ob_kg)) * rcp2(P);
 }
 
+// ------------------------------------------------------------------------------------
+// Logistic link, one-bit kinds.  z~ = +-log2(e) (thr - t) / s is the entry's signed scaled
+// argument (P = F(z~ ln 2)), so with E = exp2(-|z~|) and r = 1 / (1 + E):
+//     P = r on the near side (z~ >= 0), E r on the tail side;  1 - P is the other of the two;
+//     log2 P = log2 r + min(z~, 0):  the tail of the NLL is exactly linear, never -inf;
+//     |g| = (1 - P) / s.
+// No cancellation anywhere; an underflowing E (|z~| > 126) is exactly the limit form, so nothing
+// depends on denormals.  Pad entries sit at z~ = kPadZ: E == 0, r == 1, so log2 P == 0 and
+// g == 0 exactly.  r is returned so that the signed-row walks can take one log2 of the product
+// of four r (each in [1/2, 1]); lin = min(z~, 0) is the linear part of log2 P.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void logit_onebit_rg(f2v z, const Lik& c, f2v& r, f2v& lin, f2v& g) {
+  const f2v E = exp2_2(f2v{-__builtin_fabsf(z.x), -__builtin_fabsf(z.y)});
+  r = rcp2(splat2(1.0f) + E);
+  const f2v Er = E * r;
+  const f2v Q = f2v{z.x < 0.0f ? r.x : Er.x, z.y < 0.0f ? r.y : Er.y};  // 1 - P
+  lin = f2v{__builtin_fminf(z.x, 0.0f), __builtin_fminf(z.y, 0.0f)};
+  g = Q * splat2(c.ob_kg);
+}
+
+// F(y) and f(y) = F (1 - F) of the logistic link for two scaled arguments y (natural units)
+__device__ __forceinline__ void logit_Ff2(f2v y, f2v& F, f2v& f) {
+  const f2v E = exp2_2(f2v{__builtin_fabsf(y.x), __builtin_fabsf(y.y)} * splat2(kNegLog2e));
+  const f2v r = rcp2(splat2(1.0f) + E);
+  const f2v Er = E * r;
+  F = f2v{y.x < 0.0f ? Er.x : r.x, y.y < 0.0f ? Er.y : r.y};
+  f = Er * r;
+}
+
 // lik_grad for two entries (t.x with code c0, t.y with code c1); log2P and g of -log P.
 // Linear general kind: the caller passes t in the SCALED form t' = -t / a (its register factor
 // vector pre-multiplied by -1/a, so the dot product yields t' directly) and edges pre-divided by
@@ -395,6 +465,49 @@ __device__ __forceinline__ void lik_grad2(f2v t, int c0, int c1, bool pa, bool p
     const f2v r = x - f2v{e0.x, e1.x};
     g = splat2(2.0f) * r * tinv;
     log2P = -(r * r) * splat2(kInvLn2);
+  } else if (KIND == LIK_LOGIT_ONEBIT_SR) {
+    f2v r, lin;
+    logit_onebit_rg(t, c, r, lin, g);
+    log2P = log2_2(r) + lin;
+  } else if (KIND == LIK_LOGIT_ONEBIT) {
+    // code-field entries: z~ = z' for code 0, -z' for code 1 (pads, code 15, read as code 0)
+    const bool z0 = (c0 != 1), z1 = (c1 != 1);
+    f2v z = f2v{z0 ? t.x : -t.x, z1 ? t.y : -t.y};
+    if (pa) z.x = kPadZ;
+    if (pb) z.y = kPadZ;
+    f2v r, lin, gm;
+    logit_onebit_rg(z, c, r, lin, gm);
+    g = f2v{z0 ? gm.x : -gm.x, z1 ? gm.y : -gm.y};
+    log2P = log2_2(r) + lin;
+  } else if (KIND == LIK_LOGIT_GENERAL) {
+    // two-edge form P = F(u) - F(w), u > w.  The pair is mirrored into the lower half
+    // (F(u) - F(w) = F(-w) - F(-u); u + w <= 0 after it), where F = E r carries full relative
+    // precision, so the difference never cancels two values near 1.  f is even, so the mirror
+    // flips the sign of f(u) - f(w).  Saturated (+-1e5 or infinite) edges give E == 0, i.e.
+    // F == 0 or 1 and f == 0 exactly; no product ever meets an infinity.
+    const float2 e0 = edges[c0], e1 = edges[c1];
+    f2v u, w, tinv = splat2(1.0f);
+    if (LOG) {
+      const f2v tp = t + splat2(c.offset);
+      const f2v x = f2v{logf(tp.x), logf(tp.y)};
+      tinv = rcp2(tp);
+      u = (f2v{e0.y, e1.y} - x) * splat2(c.inv_a);
+      w = (f2v{e0.x, e1.x} - x) * splat2(c.inv_a);
+    } else {
+      u = f2v{e0.y, e1.y} + t;
+      w = f2v{e0.x, e1.x} + t;
+    }
+    const bool ma = (u.x + w.x) > 0.0f, mb = (u.y + w.y) > 0.0f;
+    const f2v uu = f2v{ma ? -w.x : u.x, mb ? -w.y : u.y};
+    const f2v ww = f2v{ma ? -u.x : w.x, mb ? -u.y : w.y};
+    f2v Fu, fu, Fw, fw;
+    logit_Ff2(uu, Fu, fu);
+    logit_Ff2(ww, Fw, fw);
+    const f2v P = Fu - Fw;
+    const f2v d = (fu - fw) * splat2(c.kgrad);
+    const f2v gm = d * rcp2(P) * tinv;
+    g = f2v{ma ? -gm.x : gm.x, mb ? -gm.y : gm.y};
+    log2P = log2_2(P);
   } else if (KIND == LIK_ONEBIT_SR) {
     f2v P;
     onebit_sr_pg(t, c, P, g);

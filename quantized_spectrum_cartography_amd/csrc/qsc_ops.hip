@@ -95,6 +95,60 @@ __global__ void __launch_bounds__(kBlock) f_probit_kernel(const float* __restric
     out[i] = phi_scaled(div_a(y[i], pr));
 }
 
+// ---------------------------------------------------------------------------------------
+// logistic link: F_logit, prob_logit forward / backward (F_sigmoid, quantization_model.py:43-47,
+// through prob_probit's edge handling, :22-39 / _log.py:23-41)
+// ---------------------------------------------------------------------------------------
+// F(z) and f(z) = F (1 - F) at the scaled argument z = y / s, from exp(-|z|) only
+__device__ __forceinline__ void logit_Ff(float z, float& F, float& f) {
+  const float e = expf(-fabsf(z));
+  const float r = 1.0f / (1.0f + e);
+  const float er = e * r;
+  F = z < 0.0f ? er : r;
+  f = er * r;
+}
+
+__global__ void __launch_bounds__(kBlock) prob_logit_kernel(const int64_t* __restrict__ Y,
+                                                            const float* __restrict__ Xh,
+                                                            int64_t n, Edges E, int nbins,
+                                                            float s, const float* __restrict__ gP,
+                                                            float* __restrict__ out) {
+  __shared__ float2 se[QSC_MAX_BOUNDS - 1];
+  for (int i = threadIdx.x; i < nbins; i += blockDim.x) se[i] = E.e[i];
+  __syncthreads();
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t y = Y[i];
+    y = y < 0 ? 0 : (y >= nbins ? nbins - 1 : y);
+    const float2 e = se[(int)y];
+    const float x = Xh[i];
+    float u = (e.y - x) / s, w = (e.x - x) / s;
+    // mirrored into the lower half, where F keeps its relative precision (lik_grad2)
+    const bool mir = (u + w) > 0.0f;
+    const float uu = mir ? -w : u, ww = mir ? -u : w;
+    float Fu, fu, Fw, fw;
+    logit_Ff(uu, Fu, fu);
+    logit_Ff(ww, Fw, fw);
+    if (gP == nullptr) {
+      out[i] = Fu - Fw;
+    } else {
+      // dP/dx = (f(w) - f(u)) / s; the mirror swaps the two
+      const float d = mir ? (fu - fw) : (fw - fu);
+      out[i] = gP[i] * (d / s);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) f_logit_kernel(const float* __restrict__ y, int64_t n,
+                                                         float s, float* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float F, f;
+    logit_Ff(y[i] / s, F, f);
+    out[i] = F;
+  }
+}
+
 __global__ void __launch_bounds__(kBlock) ordinal_kernel(const int64_t* __restrict__ Y, int64_t n,
                                                          Bounds B, int nb,
                                                          float* __restrict__ out) {
@@ -448,7 +502,7 @@ __global__ void __launch_bounds__(kBlock) perm_scatter_kernel(const float* __res
 
 extern "C" {
 
-QSC_API int qsc_version(void) { return 2; }  // 2: position-order factors are [Pp][RP]
+QSC_API int qsc_version(void) { return 3; }  // 3: QSC_LOSS_LOGIT and the qsc_*_logit ops
 
 QSC_API int qsc_rank_pad(int32_t R) {
   return (R < 1 || R > QSC_MAX_R) ? 0 : (R <= 4 ? 4 : (R <= 8 ? 8 : 16));
@@ -531,6 +585,40 @@ QSC_API int qsc_f_probit(const float* y, int64_t n, double sigma, float* out, vo
   m.sigma = sigma;
   hipLaunchKernelGGL(f_probit_kernel, dim3(grid_for(n, 4, 8192)), dim3(kBlock), 0,
                      STREAM(stream), y, n, make_probit(&m), out);
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_prob_logit(const int64_t* Y, const float* Xhat, int64_t n, const qsc_model* m,
+                           float* P, void* stream) {
+  if (!model_ok(m) || n < 0 || (n > 0 && (!Y || !Xhat || !P))) return QSC_EINVAL;
+  if (n == 0) return QSC_OK;
+  Edges E;
+  make_edges(m, &E);
+  hipLaunchKernelGGL(prob_logit_kernel, dim3(grid_for(n, 4, 8192)), dim3(kBlock), 0,
+                     STREAM(stream), Y, Xhat, n, E, m->nbounds - 1, (float)m->sigma,
+                     (const float*)nullptr, P);
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_prob_logit_bwd(const int64_t* Y, const float* Xhat, const float* gP, int64_t n,
+                               const qsc_model* m, float* gX, void* stream) {
+  if (!model_ok(m) || n < 0 || (n > 0 && (!Y || !Xhat || !gP || !gX))) return QSC_EINVAL;
+  if (n == 0) return QSC_OK;
+  Edges E;
+  make_edges(m, &E);
+  hipLaunchKernelGGL(prob_logit_kernel, dim3(grid_for(n, 4, 8192)), dim3(kBlock), 0,
+                     STREAM(stream), Y, Xhat, n, E, m->nbounds - 1, (float)m->sigma, gP, gX);
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_f_logit(const float* y, int64_t n, double scale, float* out, void* stream) {
+  if (n < 0 || !(scale > 0.0) || (n > 0 && (!y || !out))) return QSC_EINVAL;
+  if (n == 0) return QSC_OK;
+  hipLaunchKernelGGL(f_logit_kernel, dim3(grid_for(n, 4, 8192)), dim3(kBlock), 0,
+                     STREAM(stream), y, n, (float)scale, out);
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }

@@ -142,9 +142,8 @@ struct Pitch {
 // table pitch of a likelihood kind
 template <int RP, int KIND>
 struct TP {
-  static constexpr int v = KIND == LIK_ONEBIT_SR ? RP + 4 : Pitch<RP>::v;
+  static constexpr int v = is_sr(KIND) ? RP + 4 : Pitch<RP>::v;
 };
-constexpr bool is_sr(int kind) { return kind == LIK_ONEBIT_SR; }
 template <int KIND>
 __device__ constexpr bool stages_edges() {
   return !(QSC_SR_SKIP_EDGES && is_sr(KIND));
@@ -294,7 +293,7 @@ __device__ __forceinline__ float dot2s(const f2v (&own)[RP / 2], const f2v (&o)[
 template <int KIND, bool LOG>
 __device__ __forceinline__ float own_scale_of(const Lik& lk) {
   if (LOG || KIND == LIK_SQUARED) return 1.0f;
-  return (KIND == LIK_ONEBIT || KIND == LIK_ONEBIT_SR) ? -lk.ob_scale : -lk.inv_a;
+  return (is_onebit_cf(KIND) || is_sr(KIND)) ? -lk.ob_scale : -lk.inv_a;
 }
 
 struct Scalars {
@@ -486,9 +485,16 @@ __device__ __forceinline__ void pair_math(uint32_t ea, uint32_t eb, const f2v (&
     g = t * splat2(1e-3f);
     pq = splat2(1.0f) + t * splat2(1e-30f);
 #else
-    onebit_sr_pg(t, lk, pq, g);
+    if constexpr (KIND == LIK_LOGIT_ONEBIT_SR) {
+      // logistic: pq = r = 1 / (1 + E) in [1/2, 1] goes to the caller's product (log2 P =
+      // log2 r + min(z~, 0)); the linear tail part is summed here
+      f2v lin;
+      logit_onebit_rg(t, lk, pq, lin, g);
+      nll -= lin;
+    } else {
+      onebit_sr_pg(t, lk, pq, g);
+    }
 #endif
-    (void)nll;
     (void)edges;
 #pragma unroll
     for (int j = 0; j < RP / 2; ++j) acc[j] = fma2(splat2(g.x), oa[j], acc[j]);
@@ -501,7 +507,7 @@ __device__ __forceinline__ void pair_math(uint32_t ea, uint32_t eb, const f2v (&
     const int ca = (int)(ea >> T::kBits), cb = (int)(eb >> T::kBits);
     const bool pa = (ca == T::kPad) || !valid, pb = (cb == T::kPad) || !valid;
     f2v t;
-    if constexpr (KIND == LIK_ONEBIT)
+    if constexpr (is_onebit_cf(KIND))
       t = f2v{dot2z<RP>(own, oa, lk.ob_thr), dot2z<RP>(own, ob, lk.ob_thr)};
     else
       t = f2v{dot2<RP>(own, oa), dot2<RP>(own, ob)};
@@ -510,13 +516,13 @@ __device__ __forceinline__ void pair_math(uint32_t ea, uint32_t eb, const f2v (&
     g = t * splat2(1e-3f);
     log2P = t;
 #else
-    if constexpr (KIND == LIK_ONEBIT)
+    if constexpr (is_onebit_cf(KIND))
       lik_grad2<KIND, LOG>(t, ca, cb, pa, pb, edges, lk, log2P, g);
     else
       lik_grad2<KIND, LOG>(t, pa ? 0 : ca, pb ? 0 : cb, pa, pb, edges, lk, log2P, g);
 #endif
     float ga = g.x, gb = g.y;
-    if constexpr (KIND == LIK_ONEBIT) {
+    if constexpr (is_onebit_cf(KIND)) {
       nll -= log2P;  // log2 units: scaled by ln 2 later
     } else {
       ga = pa ? 0.0f : ga;
@@ -2637,8 +2643,14 @@ int spass_bpc(int RP) { return RP > 8 ? 2 : RP == 8 ? QSC_SPASS_BPC8 : QSC_SPASS
 #else
 #define QSC_DISPATCH_PASS(LAUNCH)                                                        \
   do {                                                                                   \
-    if (sr) QSC_DISPATCH_RP_NARROW(LAUNCH, LIK_ONEBIT_SR, false);                        \
+    if (sr && kind == LIK_LOGIT_ONEBIT)                                                  \
+      QSC_DISPATCH_RP_NARROW(LAUNCH, LIK_LOGIT_ONEBIT_SR, false);                        \
+    else if (sr) QSC_DISPATCH_RP_NARROW(LAUNCH, LIK_ONEBIT_SR, false);                   \
     else if (kind == LIK_ONEBIT) QSC_DISPATCH_RP(LAUNCH, LIK_ONEBIT, false);             \
+    else if (kind == LIK_LOGIT_ONEBIT) QSC_DISPATCH_RP(LAUNCH, LIK_LOGIT_ONEBIT, false); \
+    else if (kind == LIK_LOGIT_GENERAL && m->log_model)                                  \
+      QSC_DISPATCH_RP(LAUNCH, LIK_LOGIT_GENERAL, true);                                  \
+    else if (kind == LIK_LOGIT_GENERAL) QSC_DISPATCH_RP(LAUNCH, LIK_LOGIT_GENERAL, false); \
     else if (kind == LIK_SQUARED && m->log_model) QSC_DISPATCH_RP(LAUNCH, LIK_SQUARED, true); \
     else if (kind == LIK_SQUARED) QSC_DISPATCH_RP(LAUNCH, LIK_SQUARED, false);           \
     else if (m->log_model) QSC_DISPATCH_RP(LAUNCH, LIK_GENERAL, true);                   \
@@ -2879,15 +2891,15 @@ static bool sr_layout_ok(const qsc_obs_desc* d, int R) {
   return true;
 }
 
-// a launch's layout / likelihood-kind pairing: signed rows need the one-bit kind
+// a launch's layout / likelihood-kind pairing: signed rows need a one-bit kind (either link)
 static bool rowfmt_ok(const qsc_obs_desc* d, int R, int kind) {
   if (d->rowfmt == 0) return true;
-  return d->rowfmt == 1 && kind == LIK_ONEBIT && sr_layout_ok(d, R);
+  return d->rowfmt == 1 && is_onebit_cf(kind) && sr_layout_ok(d, R);
 }
 
 QSC_API int qsc_obs_signed_rows_ok(const qsc_obs_desc* d, int32_t R, const qsc_model* m) {
   if (!desc_ok(d) || !m || R < 1 || R > QSC_MAX_R || m->nbounds - 1 != d->nbins) return 0;
-  return (lik_kind(m) == LIK_ONEBIT && sr_layout_ok(d, R)) ? 1 : 0;
+  return (is_onebit_cf(lik_kind(m)) && sr_layout_ok(d, R)) ? 1 : 0;
 }
 
 QSC_API int qsc_scpass_supported(const qsc_obs_desc* d, int32_t R) {

@@ -75,8 +75,11 @@ def solve(Y, Wx, bin_boundaries, noise_std, R, offset=None, log_model=True, deco
           max_iter=500, optimize="weights", T_true=None, nmse_every=0, obs=None, tile=None,
           seed=0, callback=None, S_init=None, prefit_steps=1000, prefit_lr=1e-2, ndf=16,
           warm="residual", residual_scale=None, lr_c_rel=1e-2, calibrate=True, use_graph=True,
-          build_only=False, hist_cap=None):
+          build_only=False, hist_cap=None, loss="probit"):
     """DIP-regularised alternating probit MLE (config 5: log model + DIP prior on S).
+
+    loss: "probit" (default), "logit" (the logistic link, noise_std its scale s) or "squared",
+    as qmc.solve; ignored when a packed `obs` is given (its model decides).
 
     `offset` defaults to the reference log model's LOG_OFFSET_7_ADJUSTED
     (qmc/quantization_model_log.py:7, 9): with the zero C_init the first C-pass sees
@@ -120,7 +123,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R, offset=None, log_model=True, deco
     I, J = Y.shape[-2], Y.shape[-1]
     if obs is None:
         obs = Observations(Y, Wx, bin_boundaries, noise_std, offset=offset if log_model else 0.0,
-                           log_model=log_model, tile=tile, R_hint=R)
+                           log_model=log_model, tile=tile, R_hint=R, loss=loss)
     dev = obs.device
     fresh = decoder is None
     if fresh:

@@ -58,15 +58,17 @@ def kslab_bounds(K, world, rank):
 
 
 def kslab_observations(Y_local, Wx_local, bin_boundaries, noise_std, dist, offset=0.0,
-                       log_model=False, tile=None, R_hint=8):
-    """Observations of this rank's K-slab with the pixel order of the global counts."""
+                       log_model=False, tile=None, R_hint=8, loss="probit"):
+    """Observations of this rank's K-slab with the pixel order of the global counts (loss as in
+    obs.Observations: "probit", "logit" or "squared"; the sharded solvers read obs.model)."""
     from .obs import Observations
 
     def hook(cnt):
         dist.all_reduce(cnt)
         return cnt
     return Observations(Y_local, Wx_local, bin_boundaries, noise_std, offset=offset,
-                        log_model=log_model, tile=tile, R_hint=R_hint, count_hook=hook)
+                        log_model=log_model, tile=tile, R_hint=R_hint, count_hook=hook,
+                        loss=loss)
 
 
 

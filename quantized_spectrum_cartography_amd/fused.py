@@ -209,7 +209,9 @@ class ProbitNLL:
     log(T_hat + offset)), evaluated by the fused HIP passes over observed entries only.
 
     Replaces the reference's get_tensor -> log -> prob_probit -> log -> masked sum chain
-    (qmc/qmc.ipynb :568-572) and its autograd backward.  Usage:
+    (qmc/qmc.ipynb :568-572) and its autograd backward.  The likelihood is the one `obs` was
+    packed with (Observations(loss=...)): probit, logit (prob_logit in place of prob_probit) or
+    the squared criterion.  Usage:
         nll = ProbitNLL.apply(S, C, obs); (nll + lam*torch.norm(C)).backward()
     """
 

@@ -68,8 +68,11 @@ class Observations:
       bin_boundaries, noise_std, offset, log_model: the probit model (see quantization_model*).
       perm: optional (Pp,) int32 pixel order shared across ranks (K-slab sharding).
       tile: optional C-pass tile size (positions, multiple of 64).
-      loss: "probit" (the likelihood of qmc/qmc.ipynb) or "squared" (the Euclidean criterion
-            ||Wx (T_hat - Obs)||^2 of qmc/qmc_dowjons.ipynb :142, Obs the bin midpoints).
+      loss: "probit" (the likelihood of qmc/qmc.ipynb), "squared" (the Euclidean criterion
+            ||Wx (T_hat - Obs)||^2 of qmc/qmc_dowjons.ipynb :142, Obs the bin midpoints) or
+            "logit" (the ordered-logit likelihood: F_probit replaced by the logistic
+            F(y) = 1 / (1 + exp(-y / s)); noise_std is then the logistic scale s, the noise
+            standard deviation being s pi / sqrt(3)).
       schedule: order every packed list for bank-conflict-free LDS gathers (qsc_obs_schedule;
             default on, QSC_SCHEDULE=0 turns it off).  Results change only by summation order.
     """

@@ -475,6 +475,9 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     loss="squared" replaces the probit likelihood by the Euclidean criterion
     ||Wx (T_hat - Obs)||_F^2 of qmc/qmc_dowjons.ipynb :142-162 (Obs = bin midpoints,
     get_quantized_obs_from_ordinal); the cost history then holds that criterion.
+    loss="logit" replaces the probit link by the logistic one, F(y) = 1 / (1 + exp(-y / s)) with
+    s = noise_std (the reference's F_sigmoid at s = 1; noise standard deviation s pi / sqrt(3)):
+    every path below (free S, generator, holdout, graphs) runs the same fused passes on it.
     project_s=True keeps free S >= 0 (S[S<0] = 0 after each S-step, as C at :579).  The
     default (None) is True for the log model: it needs T_hat + offset > 0 (log at
     qmc/quantization_model_log.py:14, qmc/qmc.ipynb:571), which unprojected free S leaves within
