@@ -436,6 +436,46 @@ QSC_API int qsc_sumsq_small(const float* x, int32_t n, float* out, void* stream)
  * iteration. */
 QSC_API int qsc_adam_flat(float* p, float* m, float* v, const float* g, int64_t n,
                           const qsc_adam* adam, const qsc_state* st, void* stream);
+/* ---------------------------------------------------------------------------------------
+ * Spatial smoothness prior on the loss fields (free-S solver, qsc_smooth.hip).
+ *   R(S) = sum_{r<R} sum_{edges {p,p'}} rho(S_r(p) - S_r(p')) over the 4-neighbour graph of the
+ *   I x J pixel grid, each edge once, no edges across the border:
+ *     QSC_SMOOTH_QUAD:   rho(d) = d^2 / 2;  gradient at p: sum_n (S_r(p) - S_r(n))
+ *     QSC_SMOOTH_HUBER:  rho(d) = d^2 / (2 delta) for |d| <= delta, else |d| - delta / 2
+ *                        (smoothed anisotropic TV);  gradient: sum_n clamp((S_r(p) - S_r(n)) / delta, -1, 1)
+ *   Replaces nothing in the reference: its only S-side regulariser is lambda_s ||Z||_F
+ *   (qmc/qmc.ipynb :573, :631) and its spatial prior is the generator / decoder itself.  The
+ *   free-S solver adds smooth * R(S) to the cost of both steps and runs its S-step as
+ *   qsc_spass (mode 0) -> qsc_smooth_grad -> qsc_supdate.
+ * Workspace: qsc_smooth_workspace_bytes(Pp) bytes (0 when Pp is out of range) serve either call.
+ * Its first int32 is the history step counter of qsc_smooth_grad and belongs to the caller: zero
+ * it when a solve starts; the calls never touch the rest of its first 16 bytes.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_SMOOTH_QUAD 0
+#define QSC_SMOOTH_HUBER 1
+QSC_API size_t qsc_smooth_workspace_bytes(int32_t Pp);
+/* Neighbour table of the position order, once per observation set: nbr[Pp][4] int32 = the
+ * positions of the left, right, upper and lower grid neighbours of position q's pixel
+ * p = perm[q] = i*J + j (the inverse permutation of p-1, p+1, p-J, p+J; it is built in ws on the
+ * device), -1 outside the grid; padding positions (perm[q] == -1) get four -1.  P = I*J <= Pp. */
+QSC_API int qsc_smooth_neighbors(const int32_t* perm, int32_t P, int32_t Pp, int32_t I, int32_t J,
+                                 int32_t* nbr, void* ws, size_t ws_bytes, void* stream);
+/* dS[q][r] += weight * dR/dS[q][r] for r < R (dS as qsc_spass mode 0 wrote it; rows r >= R and
+ * positions without neighbours, the padding ones among them, are not written; dS nullable:
+ * penalty only) and *pen = R(S), unweighted (pen nullable when pen_hist is given).  S, dS in
+ * position order [Pp][RP]; every row and neighbour row is read as whole 16-byte vectors.
+ * Deterministic: wave sums, one partial per block in ws, then a fixed-order sum -- no
+ * floating-point atomics.  pen_hist (nullable): a [hist_cap] float history; the row written is
+ * the workspace's step counter (rows >= hist_cap are dropped, as qsc_cfinish drops its own),
+ * which the call then increments on the device -- so the call can be captured into every
+ * iteration of a replayed hipGraph.  (The counter is not qsc_state.iter: that one is settled
+ * through the deferred `pending` protocol.)  delta is read for QSC_SMOOTH_HUBER only (> 0).
+ * QSC_EUNSUPPORTED when Pp exceeds the supported 2^28 positions. */
+QSC_API int qsc_smooth_grad(const float* S, const int32_t* nbr, int32_t R, int32_t Pp,
+                            int32_t kind, float delta, float weight, float* dS, float* pen,
+                            float* pen_hist, int32_t hist_cap, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* debug builds (QSC_DEBUG=1, _build.py --debug): the source line of the last failed bounds
  * check in the pass kernels (entry offsets, gather-table rows, lane bins; a failed check is
  * recorded and its index clamped, never trapped), 0 if none, -1 in release builds.

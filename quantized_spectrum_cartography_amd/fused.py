@@ -18,6 +18,30 @@ from . import _lib
 from ._model import _dev, _ws
 
 
+SMOOTH_KINDS = {"quad": 0, "huber": 1}  # QSC_SMOOTH_QUAD, QSC_SMOOTH_HUBER
+
+
+def smooth_kind(kind, delta):
+    """(kind code, delta) of the smoothness prior, validated: kind "quad" or "huber", the latter
+    with delta > 0."""
+    if kind not in SMOOTH_KINDS:
+        raise ValueError("smooth_kind must be one of %s, got %r" % (sorted(SMOOTH_KINDS), kind))
+    if kind == "huber":
+        if delta is None or not float(delta) > 0.0:
+            raise ValueError("smooth_kind='huber' needs smooth_delta > 0")
+        return SMOOTH_KINDS[kind], float(delta)
+    return SMOOTH_KINDS[kind], 0.0
+
+
+def check_smooth(smooth, kind, delta):
+    """Validate the solver's smoothness arguments; returns float(smooth)."""
+    smooth = float(smooth)
+    if not smooth >= 0.0:
+        raise ValueError("smooth must be >= 0, got %r" % (smooth,))
+    smooth_kind(kind, delta)
+    return smooth
+
+
 class PassEngine:
     """Workspace + device state for running the fused passes on one Observations set."""
 
@@ -166,6 +190,39 @@ class PassEngine:
         _lib.call("qsc_state_flush", self.desc, self.R, _lib.ptr(self.state), _lib.ptr(hist),
                   cap, _lib.ptr(self.ws), self.ws.numel(), _lib.stream())
 
+    # ---- smoothness prior ---------------------------------------------------------------
+    def _smooth_bufs(self):
+        """The prior's workspace (zeroed: its first word is the history step counter), the
+        device scalar R(S) of the last call and the per-iteration history (hist_cap rows)."""
+        if getattr(self, "smooth_ws", None) is None:
+            dev = self.obs.device
+            nb = _lib.lib().qsc_smooth_workspace_bytes(self.obs.Pp)
+            if nb == 0:
+                raise _lib.QscError("the smoothness prior does not support Pp = %d" % self.obs.Pp)
+            self.smooth_ws = torch.zeros(int(nb), dtype=torch.uint8, device=dev)
+            self.pen = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.pen_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float32, device=dev)
+        return self.smooth_ws
+
+    def smooth_grad(self, S_pos, dS, kind="quad", delta=None, weight=1.0, record=True):
+        """dS += weight * grad R(S) (dS None: value only) and R(S) -> self.pen (qsc_smooth_grad);
+        with `record` (and a history) the value is also appended to the penalty history, at the
+        row the device-side step counter says."""
+        ws = self._smooth_bufs()
+        code, delta = smooth_kind(kind, delta)
+        hist, cap = (self.pen_hist, self.hist_cap) if (record and self.hist_cap) else (None, 0)
+        _lib.call("qsc_smooth_grad", _lib.ptr(S_pos), _lib.ptr(self.obs.neighbors()), self.R,
+                  self.obs.Pp, code, delta, float(weight), _lib.ptr(dS), _lib.ptr(self.pen),
+                  _lib.ptr(hist), cap, _lib.ptr(ws), ws.numel(), _lib.stream())
+        return self.pen
+
+    def smooth_history(self):
+        """R(S) of every recorded smooth_grad call so far, in order (fp64 list; synchronises)."""
+        if getattr(self, "smooth_ws", None) is None:
+            return []
+        n = min(int(self.smooth_ws[:4].view(torch.int32).item()), self.hist_cap)
+        return self.pen_hist[:n].double().cpu().tolist()
+
     # ---- composite ----------------------------------------------------------------------
     def nll_grad(self, S_pos, C, need_dS=True, need_dC=True):
         """NLL (device scalar) and its gradients dS (position order) and dC, no regularisers."""
@@ -220,3 +277,34 @@ class ProbitNLL:
         if S.dim() == 3:
             S = S.unsqueeze(1)
         return _ProbitNLLFn.apply(S, C, obs)
+
+
+def smooth_penalty(S, kind="quad", delta=None):
+    """(R(S), grad R(S)) of the smoothness prior solve(smooth=...) adds, for loss fields S in
+    pixel order, a (R,1,I,J) or (R,I,J) GPU tensor: R(S) a 0-dim fp32 GPU tensor (unweighted), the
+    gradient shaped like S.  Runs the solver's own kernel (qsc_smooth_grad) on the identity
+    pixel order, so it evaluates exactly the prior the solver applies."""
+    from .obs import neighbor_table
+    code, delta = smooth_kind(kind, delta)
+    _lib.require_device(S)
+    R, I, J = S.shape[0], S.shape[-2], S.shape[-1]
+    P = I * J
+    RP = int(_lib.lib().qsc_rank_pad(R))
+    if RP == 0:
+        raise ValueError("rank R must be in [1, %d]" % _lib.QSC_MAX_R)
+    dev = S.device
+    nat = S.detach().to(torch.float32).reshape(R, P).contiguous()
+    perm = torch.arange(P, dtype=torch.int32, device=dev)
+    nbr = neighbor_table(perm, I, J)
+    pos = torch.empty((P, RP), dtype=torch.float32, device=dev)
+    _lib.call("qsc_perm_gather", _lib.ptr(nat), _lib.ptr(perm), R, P, P, _lib.ptr(pos),
+              _lib.stream())
+    g_pos = torch.zeros_like(pos)
+    ws = torch.zeros(int(_lib.lib().qsc_smooth_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+    pen = torch.zeros(1, dtype=torch.float32, device=dev)
+    _lib.call("qsc_smooth_grad", _lib.ptr(pos), _lib.ptr(nbr), R, P, code, delta, 1.0,
+              _lib.ptr(g_pos), _lib.ptr(pen), None, 0, _lib.ptr(ws), ws.numel(), _lib.stream())
+    grad = torch.empty((R, P), dtype=torch.float32, device=dev)
+    _lib.call("qsc_perm_scatter", _lib.ptr(g_pos), _lib.ptr(perm), R, P, P, _lib.ptr(grad),
+              _lib.stream())
+    return pen[0], grad.reshape(S.shape)

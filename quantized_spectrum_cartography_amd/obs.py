@@ -59,6 +59,21 @@ def default_tile(P, R, K):
     return t
 
 
+def neighbor_table(perm, I, J):
+    """(Pp, 4) int32 neighbour positions (left, right, up, down; -1 = none) of the pixel order
+    `perm` ((Pp,) int32 on the GPU, -1 = padding) over the I x J grid: qsc_smooth_neighbors."""
+    _lib.require_device(perm)
+    Pp = perm.numel()
+    nb = _lib.lib().qsc_smooth_workspace_bytes(Pp)
+    if nb == 0:
+        raise _lib.QscError("qsc_smooth_workspace_bytes: %d positions are out of range" % Pp)
+    ws = _ws(nb, perm.device)
+    nbr = torch.empty((Pp, 4), dtype=torch.int32, device=perm.device)
+    _lib.call("qsc_smooth_neighbors", _lib.ptr(perm), I * J, Pp, I, J, _lib.ptr(nbr),
+              _lib.ptr(ws), ws.numel(), _lib.stream())
+    return nbr
+
+
 class Observations:
     """Packed observations of one K-slab.
 
@@ -231,6 +246,16 @@ class Observations:
                                                        device=self.device)[valid]
             self._iperm = ip
         return ip
+
+    def neighbors(self):
+        """(Pp, 4) int32: the positions of every position's left, right, upper and lower grid
+        neighbour, -1 outside the grid and for padding positions (qsc_smooth_neighbors; cached).
+        The table of the smoothness prior (qsc_smooth_grad)."""
+        nb = getattr(self, "_nbr", None)
+        if nb is None:
+            nb = neighbor_table(self.perm, self.I, self.J)
+            self._nbr = nb
+        return nb
 
     def to_positions(self, X, out=None):
         """(R, P) natural pixel order -> (Pp, RP) position order (pixel-major rows, zero padded);

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._model import _dev, map_nmse
-from .fused import PassEngine
+from .fused import PassEngine, check_smooth
 from .obs import Observations
 from .utils import LOG_OFFSET_7_ADJUSTED as LOG_OFFSET
 
@@ -296,7 +296,10 @@ class FreeSSolver:
 
     def __init__(self, obs, S_init, C_init, lambda_c=100.0, lambda_s=100.0, lr_c=5e-3, lr_s=1e-2,
                  betas=(0.9, 0.999), eps=1e-8, project_c=True, hist_cap=1024, fuse=True,
-                 T_true=None, nmse_every=0, project_s=None, chain=True):
+                 T_true=None, nmse_every=0, project_s=None, chain=True, smooth=0.0,
+                 smooth_kind="quad", smooth_delta=None):
+        self.smooth = check_smooth(smooth, smooth_kind, smooth_delta)
+        self.smooth_kind, self.smooth_delta = smooth_kind, smooth_delta
         self.obs = obs
         R = S_init.shape[0]
         self.R = R
@@ -324,6 +327,15 @@ class FreeSSolver:
         self.chain = bool(chain)
         self._ahead, self._ahead_ver = False, None
         self._graphs = {}
+        if self.smooth > 0.0:
+            # smoothness prior smooth * R(S) (qsc_smooth_grad): the S-step becomes gradient pass
+            # -> prior gradient -> Adam (three launches and a one-block finish), so neither the
+            # fused launch (its S-step takes no external gradient term) nor run chaining applies
+            self.fuse = False
+            self.chain = False
+            self.dS_buf = torch.zeros_like(self.S)
+            obs.neighbors()  # (built here, outside any capture)
+            self.engine._smooth_bufs()
         # map NMSE after every `nmse_every`-th S-step, on the device inside the iteration
         # sequence (qsc_map_nmse_track; the reference evaluates it every iteration, :582, :637)
         self.nmse_every = int(nmse_every) if T_true is not None else 0
@@ -345,6 +357,14 @@ class FreeSSolver:
     def s_step(self):
         e = self.engine
         self._ahead = False
+        if self.smooth > 0.0:
+            # dS = NLL gradient, += smooth * grad R(S) (R(S) into the penalty history), then
+            # qsc_supdate: + lambda_s S/||S||, Adam, the S >= 0 projection
+            e.spass(self.S, self.C, 0, dS=self.dS_buf)
+            e.smooth_grad(self.S, self.dS_buf, self.smooth_kind, self.smooth_delta, self.smooth)
+            e.supdate(self.S, self.mS, self.vS, self.dS_buf, self.adam_s, self.lambda_s)
+            self._track()
+            return
         e.spass(self.S, self.C, 1, mS=self.mS, vS=self.vS, adam=self.adam_s, lambda_s=self.lambda_s)
         self._track()
 
@@ -451,12 +471,18 @@ class FreeSSolver:
         n = min(int(st["iter"]), self.engine.hist_cap)
         h = self.engine.hist[: 4 * n].view(n, 4).double().cpu()
         nsq_c_final = float((self.C.double() ** 2).sum().item())
+        # smooth * R(S) at the S both steps of iteration i were evaluated with (the S before
+        # S-step i), recorded by that S-step's qsc_smooth_grad
+        pen = self.engine.smooth_history() if self.smooth > 0.0 else []
         costs_c, costs_s = [], []
         for i in range(n):
             nll_c, nll_s, nsq_c, nsq_s = h[i].tolist()
             nsq_c_next = h[i + 1][2].item() if i + 1 < n else nsq_c_final
-            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + self.lambda_s * math.sqrt(nsq_s))
-            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_c_next) + self.lambda_s * math.sqrt(nsq_s))
+            prior = self.smooth * pen[i] if i < len(pen) else 0.0
+            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + self.lambda_s * math.sqrt(nsq_s)
+                           + prior)
+            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_c_next) + self.lambda_s * math.sqrt(nsq_s)
+                           + prior)
         return costs_c, costs_s
 
 
@@ -465,7 +491,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           betas=(0.9, 0.999), eps=1e-8, project_c=True, generator=None, Z_init=None,
           restart=False, restart_samples=(200, 200), T_true=None, nmse_every=0,
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
-          project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0):
+          project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
+          smooth=0.0, smooth_kind="quad", smooth_delta=None):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -490,8 +517,25 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     `patience` checks, returning the S, C of the best check (result.best_iter, .holdout_nll).
     With ~6 one-bit samples per pixel (C2) the unregularised free-S MLE over-fits: the map
     NMSE is best after ~50 iterations and grows after.
+    smooth > 0 (free S only; not in the reference, whose spatial prior is the generator): adds
+    the smoothness prior smooth * R(S) on the loss fields to the cost of both steps, R summed
+    over the 4-neighbour edges {p, p'} of the I x J grid (each once, none across the border) and
+    over the emitters r:  smooth_kind="quad": R = 1/2 sum (S_r(p) - S_r(p'))^2 (Tikhonov);
+    "huber": R = sum h(S_r(p) - S_r(p')), h(d) = d^2 / (2 delta) for |d| <= delta else
+    |d| - delta / 2, delta = smooth_delta > 0 (a smoothed anisotropic TV that keeps edges).  The
+    S-step then runs as gradient pass -> prior gradient (qsc_smooth_grad, a HIP kernel in the
+    solver's pixel order) -> Adam, without the fused S-step + C-pass launch (result.fused is
+    False); the cost histories include the prior.  Pixels without observations then follow
+    their neighbours instead of only shrinking.  holdout= is a natural way to pick `smooth`.
+    Raises ValueError for smooth < 0, an unknown kind, huber without delta > 0, or smooth > 0
+    with a generator (which is itself the prior).  smooth = 0 (default) is the unregularised
+    path, unchanged.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
+    smooth = check_smooth(smooth, smooth_kind, smooth_delta)
+    if smooth > 0.0 and generator is not None:
+        raise ValueError("smooth > 0 applies to free S only: a generator already carries the "
+                         "spatial prior")
     if log_model and obs is None:
         # the reference log model's default offset (qmc/quantization_model_log.py:7, 9)
         offset = LOG_OFFSET if offset is None else float(offset)
@@ -522,7 +566,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     if generator is None and obs_h is not None:
         return _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
                               max_iter, betas, eps, project_c, fuse, project_s, use_graph,
-                              int(check_every), int(patience))
+                              int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
     if generator is None:
         if S_init is None:
             S_init = torch.zeros(R, 1, I, J)
@@ -536,7 +580,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         sol = FreeSSolver(obs, S_init, C_init, lambda_c, lambda_s, lr_c, lr_s, betas, eps,
                           project_c, hist_cap=max_iter, fuse=fuse,
                           T_true=T_true if nmse_every else None, nmse_every=nmse_every,
-                          project_s=project_s)
+                          project_s=project_s, smooth=smooth, smooth_kind=smooth_kind,
+                          smooth_delta=smooth_delta)
         done = 0
         chunk = nmse_every if (callback is not None and nmse_every) else max_iter
         while done < max_iter:
@@ -784,13 +829,16 @@ def split_holdout(Y, Wx, frac, seed=0):
 
 
 def _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s, max_iter,
-                   betas, eps, project_c, fuse, project_s, use_graph, check_every, patience):
-    """Free-S solve with early stopping on the held-out NLL (solve(holdout=...))."""
+                   betas, eps, project_c, fuse, project_s, use_graph, check_every, patience,
+                   smooth=0.0, smooth_kind="quad", smooth_delta=None):
+    """Free-S solve with early stopping on the held-out NLL (solve(holdout=...)); the held-out
+    criterion is the NLL alone, also with a smoothness prior on the fit."""
     I, J = obs.I, obs.J
     if S_init is None:
         S_init = torch.zeros(R, 1, I, J)
     sol = FreeSSolver(obs, S_init, C_init, lambda_c, lambda_s, lr_c, lr_s, betas, eps, project_c,
-                      hist_cap=max_iter, fuse=fuse, project_s=project_s)
+                      hist_cap=max_iter, fuse=fuse, project_s=project_s, smooth=smooth,
+                      smooth_kind=smooth_kind, smooth_delta=smooth_delta)
     eng_h = PassEngine(obs_h, R)
     eng_h.init_state(sol.S)
     dS_h = torch.empty_like(sol.S)

@@ -81,3 +81,10 @@ def find_boundaries(samples, num_bins=4):
         edges.append(data[-1].item())
     sd = min(edges[i + 1] - edges[i] for i in range(len(edges) - 1))
     return edges, sd
+
+
+def smooth_penalty(S, kind="quad", delta=None):
+    """(value, grad) of the spatial smoothness prior of qmc.solve(smooth=...) for pixel-order
+    loss fields S (R,1,I,J) on the GPU -- fused.smooth_penalty (the solver's own HIP kernel)."""
+    from .fused import smooth_penalty as _sp
+    return _sp(S, kind, delta)
