@@ -476,10 +476,13 @@ QSC_API int qsc_smooth_grad(const float* S, const int32_t* nbr, int32_t R, int32
                             float* pen_hist, int32_t hist_cap, void* ws, size_t ws_bytes,
                             void* stream);
 
-/* debug builds (QSC_DEBUG=1, _build.py --debug): the source line of the last failed bounds
- * check in the pass kernels (entry offsets, gather-table rows, lane bins; a failed check is
- * recorded and its index clamped, never trapped), 0 if none, -1 in release builds.
- * SYNCHRONOUS (device synchronise); clear != 0 resets the flag. */
+/* debug builds (QSC_DEBUG=1, _build.py --debug): the last failed bounds check in the pass
+ * kernels (entry offsets, gather-table rows, lane bins; a failed check is recorded and its index
+ * clamped, never trapped) as file id * 100000 + source line, 0 if none, -1 in release builds,
+ * -2 if the device could not be read.  Every pass kernel file keeps a flag of its own; they are
+ * asked in the order of their ids -- 1: qsc_pass_s.hip, 2: qsc_pass_c.hip, 3: qsc_pass_fused.hip
+ * -- and the first flag set is returned (the line is that file's, or one of qsc_pass.cuh, which
+ * holds the walks they share).  SYNCHRONOUS (device synchronise); clear != 0 resets all flags. */
 QSC_API int qsc_debug_status(int32_t clear);
 /* diagnostics: out[0..n) = ocml erff(x), out[n..2n) = the erf of the fused passes (erf_fast) */
 QSC_API int qsc_selftest_erf(const float* x, int32_t n, float* out, void* stream);

@@ -13,8 +13,11 @@ import tempfile
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libqsc_hip.so")
-SOURCES = ["qsc_ops.hip", "qsc_obs.hip", "qsc_pass.hip", "qsc_gram.hip", "qsc_spa.hip",
-           "qsc_map.hip", "qsc_smooth.hip"]
+# the fused passes (qsc_pass.cuh), one translation unit per kernel family so that they compile
+# side by side
+PASS_SOURCES = ["qsc_pass_s.hip", "qsc_pass_c.hip", "qsc_pass_fused.hip", "qsc_pass_finish.hip"]
+SOURCES = PASS_SOURCES + ["qsc_ops.hip", "qsc_obs.hip", "qsc_gram.hip", "qsc_spa.hip",
+                          "qsc_map.hip", "qsc_smooth.hip"]
 ARCH = os.environ.get("QSC_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: hipcc contracts a*b+c into FMA by default, which would change the
 # reference's separately rounded products and sums (get_tensor, quantize); FMAs that are
@@ -22,11 +25,12 @@ ARCH = os.environ.get("QSC_OFFLOAD_ARCH", "gfx950")
 # lanes into v_pk_* ops costs a v_mov per operand and s_nop hazards in the fused passes.
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall",
           "-Wno-unused-function", "-ffp-contract=off", "-fno-slp-vectorize"]
-# per-source flags.  qsc_pass.hip (the fused passes) runs with f32 denormals flushed: the
+# per-source flags.  The fused passes (PASS_SOURCES) run with f32 denormals flushed: the
 # one-bit likelihood carries its tail probability 2^-101 low so that tails below 2^-25 (where the
 # reference's fp32 erf saturates, P == 0) underflow to exactly 0 without a compare per entry
 # (QSC_FTZ_SAT, qsc_common.cuh lik_grad2).
-FILE_FLAGS = {"qsc_pass.hip": ["-fgpu-flush-denormals-to-zero", "-DQSC_FTZ_SAT=1"]}
+PASS_FLAGS = ["-fgpu-flush-denormals-to-zero", "-DQSC_FTZ_SAT=1"]
+FILE_FLAGS = {src: PASS_FLAGS for src in PASS_SOURCES}
 
 
 def _hipcc():

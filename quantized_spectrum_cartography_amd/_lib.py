@@ -131,6 +131,7 @@ def err(code):
 # QSC_DEBUG_CHECK=1 (with a QSC_DEBUG=1 library, _build.py --debug): after every call outside
 # graph capture, synchronise and raise if a kernel bounds check failed (qsc_debug_status)
 _DEBUG_CHECK = os.environ.get("QSC_DEBUG_CHECK", "0") == "1"
+_DEBUG_FILES = {1: "qsc_pass_s.hip", 2: "qsc_pass_c.hip", 3: "qsc_pass_fused.hip"}
 
 
 def call(name, *args):
@@ -139,10 +140,14 @@ def call(name, *args):
     if rc != 0:
         raise QscError("%s failed: %s (code %d)" % (name, err(rc), rc))
     if _DEBUG_CHECK and not torch.cuda.is_current_stream_capturing():
-        line = lib().qsc_debug_status(1)
-        if line > 0:
-            raise QscError("%s: kernel bounds check failed at qsc_pass.hip:%d (QSC_DEBUG)"
-                           % (name, line))
+        status = lib().qsc_debug_status(1)
+        if status > 0:
+            # file id * 100000 + line (include/qsc.h); the checks of the shared walk code carry
+            # their line in qsc_pass.cuh
+            fid, line = divmod(status, 100000)
+            src = _DEBUG_FILES.get(fid, "pass kernel file %d" % fid)
+            raise QscError("%s: kernel bounds check failed in %s at line %d (of that file, or of "
+                           "qsc_pass.cuh which it includes) (QSC_DEBUG)" % (name, src, line))
     return rc
 
 

@@ -202,15 +202,15 @@ struct Lik {
 // QSC_DEBUG=1 builds (_build.py --debug): bounds checks in the pass kernels.  A failed check
 // never traps (a GPU exception can take the whole node down): it records the line in a device
 // flag, the offending index is clamped into range so the kernel finishes, and the host reads
-// the flag with qsc_debug_status after the call.
+// the flag with qsc_debug_status after the call.  (The flag is file-local, one per pass kernel
+// file: qsc_pass.cuh.)
 #ifndef QSC_DEBUG
 #define QSC_DEBUG 0
 #endif
 #if QSC_DEBUG
-extern __device__ int g_qsc_dbg_line;
-#define QSC_DCHECK(c)                                      \
-  do {                                                     \
-    if (!(c)) atomicMax(&::qsc::g_qsc_dbg_line, __LINE__); \
+#define QSC_DCHECK(c)                               \
+  do {                                              \
+    if (!(c)) atomicMax(&g_qsc_dbg_line, __LINE__); \
   } while (0)
 #else
 #define QSC_DCHECK(c) \

@@ -1,7 +1,7 @@
 // qsc_ops.hip — elementwise model ops, reconstruction and reductions (gfx950).
 //
 // These back the reference's module-level functions one to one (see include/qsc.h for the
-// file:line of each); the fused solver passes live in qsc_pass.hip.
+// file:line of each); the fused solver passes live in qsc_pass.cuh and the qsc_pass_*.hip files.
 #include <string.h>
 
 #include "qsc_common.cuh"

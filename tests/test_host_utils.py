@@ -61,7 +61,7 @@ def test_every_package_module_imports():
 
 
 def _fin_arrive(ctr, t, nt, nvb, G_max=8):
-    """The fused-finish arrival protocol of fin_arrive (csrc/qsc_pass.hip), restated: tile t
+    """The fused-finish arrival protocol of fin_arrive (csrc/qsc_pass_*.hip), restated: tile t
     counts on its group's counter (group g = t mod G, G = min(8, nt), n_g tiles); the group's
     last arrival counts the group complete; the last q_g arrivals of group g run C-finish items
     g, g + G, ... once the completed-group count reaches (launch + 1) G.  Counters are 64-bit and

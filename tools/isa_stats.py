@@ -1,6 +1,8 @@
 """Register use / spills of the kernels in a gfx950 assembly listing, and an instruction histogram
 of one kernel's body (diagnostic; the listing comes from
-  hipcc <library CFLAGS> --cuda-device-only -S quantized_spectrum_cartography_amd/csrc/qsc_pass.hip -o pass.s)
+  hipcc <library CFLAGS> --cuda-device-only -S quantized_spectrum_cartography_amd/csrc/qsc_pass_fused.hip -o pass.s;
+  the pass kernels are in qsc_pass_s / _c / _fused / _finish.hip, with the flags of _build.PASS_FLAGS;
+  tools/isa_compare.py compares two such builds kernel by kernel)
 
   python tools/isa_stats.py pass.s [kernel-substring [line-range a:b]]
 """

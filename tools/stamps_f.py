@@ -34,7 +34,7 @@ def main():
     us = ev0.elapsed_time(ev1) * 1e3
     n = 4096 * 32
     buf = (ctypes.c_ulonglong * n)()
-    assert _lib.lib().qsc_diag_stamps(buf, n) == 0
+    assert _lib.lib().qsc_diag_stamps_fused(buf, n) == 0
     st = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 32).astype(np.int64)
     st = st[st[:, 0] > 0]
     r0 = st[:, 28].min()

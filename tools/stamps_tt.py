@@ -29,7 +29,7 @@ def main():
     torch.cuda.synchronize()
     n = 4096 * 32
     buf = (ctypes.c_ulonglong * n)()
-    assert _lib.lib().qsc_diag_stamps(buf, n) == 0
+    assert _lib.lib().qsc_diag_stamps_fused(buf, n) == 0
     st = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 32).astype(np.int64)
     ghz = np.median((st[:, 31] - st[:, 0]) / np.maximum(st[:, 29] - st[:, 28], 1)) * 0.1
     us = lambda c: c / (ghz * 1e3)
