@@ -476,6 +476,63 @@ QSC_API int qsc_smooth_grad(const float* S, const int32_t* nbr, int32_t R, int32
                             float* pen_hist, int32_t hist_cap, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-pixel confidence from Fisher information (qsc_info.hip).
+ *   Conditional on C, the Hessian of the NLL with respect to S is block diagonal: position q has
+ *     J_q = sum_{k observed at q} h(k, q) c_k c_k^T,  c_k = C[:, k]                   (R x R)
+ *   with h the curvature of one entry's -log P in t = T_hat[k, q].  In the model domain x
+ *   (x = t, or log(t + offset)), with phi = F' the link's density:
+ *     P   = F(hi - x) - F(lo - x)           (the edge handling of prob_probit / prob_logit)
+ *     P'  = -(phi(hi - x) - phi(lo - x)),  P'' = phi'(hi - x) - phi'(lo - x),  g_x = -P'/P
+ *     QSC_INFO_OBSERVED:  h_x = (P'/P)^2 - P''/P at the entry's own code (what a double backward
+ *                         of the NLL gives)
+ *     QSC_INFO_EXPECTED:  h_x = sum_b (P_b')^2 / P_b over all nbins bins, bins with P_b == 0
+ *                         dropped: independent of the code and >= 0, the Fisher information of
+ *                         the Cramer-Rao bound
+ *     probit: a = fp32(sigma * 1.414213), phi(y) = exp(-(y/a)^2) / (a sqrt(pi)),
+ *             P'' = -(2 u phi(u) - 2 w phi(w)) / a,  u = (hi - x)/a, w = (lo - x)/a
+ *     logit:  phi = F (1 - F) / s,  phi' = phi (1 - 2F) / s
+ *     A saturated or infinite edge contributes exactly 0 to phi and to z phi; an entry whose P
+ *     underflows to 0 contributes 0.
+ *     linear model: h = h_x;  log model: observed h = (h_x - g_x) / (t + offset)^2 (it may be
+ *     negative, so J_q may be indefinite: that is the Hessian, not an error), expected
+ *     h = h_x / (t + offset)^2.
+ *   C is treated as known (its R K parameters are informed by millions of entries); the C-side
+ *   information and a joint covariance are not computed.  Replaces nothing in the reference,
+ *   which returns point estimates only.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_INFO_EXPECTED 0
+#define QSC_INFO_OBSERVED 1
+/* Information blocks J[Pp][RP][RP] (fp32, full symmetric blocks in position order,
+ * RP = qsc_rank_pad(R), rows and columns >= R zero) from one walk over the S-format lists of any
+ * layout qsc_obs_fill produces (narrow / wide, rowfmt 0 / 1); S in position order [Pp][RP],
+ * C [R][K].  Pad entries add exactly 0; positions without observations and padding positions get
+ * an all-zero block (written, not skipped).  Each block is summed by its position's two lanes in
+ * list order -- no floating-point atomics, two calls agree bit for bit.  No workspace.
+ * QSC_EINVAL for m->loss == QSC_LOSS_SQUARED (not a likelihood) and for a layout / model
+ * mismatch; QSC_EUNSUPPORTED when C^T (K rows of RP (+4) floats) and the bin edges exceed the
+ * 160 KiB of LDS. */
+QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                      const int64_t* s_off, const qsc_model* m, int32_t R, const float* S,
+                      const float* C, int32_t kind, float* J, void* stream);
+/* Standard deviations from the blocks, one Cholesky of J_q + ridge I (R x R) per position:
+ *   std_S[Pp][RP] = sqrt(diag((J_q + ridge I)^-1)), position order, rows >= R zero;
+ *   std_T[K][P] (nullable; pixel order through perm, p = perm[q]) =
+ *     sqrt(c_k^T (J_p + ridge I)^-1 c_k), the delta-method standard deviation of the map entry
+ *     T_hat[k, p], observed or not.
+ * A non-positive pivot marks the whole position unidentified: its std_S (rows < R) and std_T are
+ * +inf, never NaN, and it is counted into *nbad (device int32, the caller zeroes it; integer
+ * atomics only, so the call is deterministic).  Padding positions (perm[q] < 0) are not
+ * factored and not counted; their std_S rows are written as 0.  ridge >= 0.  No workspace. */
+QSC_API int qsc_info_std(const float* J, const int32_t* perm, int32_t R, int32_t P, int32_t Pp,
+                         const float* C, int32_t K, float ridge, float* std_S, float* std_T,
+                         int32_t* nbad, void* stream);
+/* Elementwise curvature h of -log P(Y | t) in the map value t = T[i] (the device function of
+ * qsc_sinfo: same formulas, same chain through log(t + offset) in the log model), kind as above;
+ * Y outside [0, nbins) is clamped as qsc_prob_probit clamps it. */
+QSC_API int qsc_entry_info(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
+                           int32_t kind, float* H, void* stream);
+
 /* debug builds (QSC_DEBUG=1, _build.py --debug): the last failed bounds check in the pass
  * kernels (entry offsets, gather-table rows, lane bins; a failed check is recorded and its index
  * clamped, never trapped) as file id * 100000 + source line, 0 if none, -1 in release builds,

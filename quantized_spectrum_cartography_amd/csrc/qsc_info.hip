@@ -1,0 +1,575 @@
+// qsc_info.hip — per-pixel Fisher information of the loss fields and the standard deviations it
+// implies (include/qsc.h: qsc_sinfo, qsc_info_std, qsc_entry_info).
+//
+// Conditional on C, the Hessian of the NLL with respect to S is block diagonal; position q has
+//     J_q = sum_{k observed at q} h(k, q) c_k c_k^T,   c_k = C[:, k]                  (R x R)
+// with h the curvature of one entry's -log P in t = T_hat[k, q].  In the model domain x (x = t,
+// or log(t + offset)), with u = (hi - x) / a, w = (lo - x) / a, phi = F':
+//     P   = F(hi - x) - F(lo - x)
+//     P'  = -(phi(hi - x) - phi(lo - x))
+//     P'' = phi'(hi - x) - phi'(lo - x)
+//     g_x = -P' / P
+//     observed:  h_x = (P'/P)^2 - P''/P  at the entry's own code
+//     expected:  h_x = sum_b (P_b')^2 / P_b  over all bins (bins with P_b == 0 dropped)
+//   probit:  phi(y) = exp(-(y/a)^2) / (a sqrt(pi)),  P'' = -(2 u phi(u) - 2 w phi(w)) / a
+//   logit:   phi = F (1 - F) / s,                    phi' = phi (1 - 2 F) / s
+//   chain:   linear h = h_x;  log model observed h = (h_x - g_x) / (t + offset)^2,
+//            expected h = h_x / (t + offset)^2
+// The reference has no counterpart (it returns point estimates only).
+//
+// Numerics.  A bin's pair (u, w) is mirrored into the lower half first ((u, w) -> (-w, -u) when
+// u + w > 0: P and P'' are unchanged, P' changes sign), where F is evaluated as a tail
+// (0.5 erfc(-z), or E / (1 + E)) at full relative precision, so P never cancels two values near 1.
+// A saturated or infinite edge (|z| beyond kSatProbit / kSatLogit, where phi is 0 in fp32)
+// contributes exactly 0 to phi and to z phi: no product meets an infinity.  An entry whose P
+// underflows to 0 has no representable curvature and contributes 0.
+//
+// qsc_sinfo walks the S-format lists as the S-pass does: one wave per slice of QSC_SLICE
+// positions, two lanes per position; lane half h takes entries 2h, 2h + 1 of every 4-entry chunk
+// in list order and keeps the upper triangle of its partial block in registers; the halves are
+// added once (a + b is the same bits on both lanes) and each half writes RP / 2 rows of the full
+// symmetric block.  No atomics: the order of every sum is fixed by the packing alone.
+// qsc_info_std: one thread per position, Cholesky of J_q + ridge I in registers, the triangular
+// inverse in place; std_S from its column norms, std_T[k] = |L^-1 c_k|.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "qsc_common.cuh"
+
+namespace {
+using namespace qsc;
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr size_t kInfoLdsMax = 160 * 1024;  // the LDS of one CU, as the passes' bound
+constexpr float kSatProbit = 14.0f;   // exp(-z^2) == 0 in fp32 from |z| = 10.2 on
+constexpr float kSatLogit = 100.0f;   // exp(-|z|) is denormal from |z| = 87.3 on
+
+enum { INFO_EXPECTED = QSC_INFO_EXPECTED, INFO_OBSERVED = QSC_INFO_OBSERVED };
+
+// per-call constants of the link
+struct Link {
+  float a, inv_a;  // probit: fp32(sigma * 1.414213); logit: the scale s
+  float k1;        // probit: 1 / (a sqrt(pi));  logit: 1 / s
+  float offset;
+  int nbins;
+};
+
+inline Link make_link(const qsc_model* m) {
+  Link l;
+  if (m->loss == QSC_LOSS_LOGIT) {
+    l.a = (float)m->sigma;
+    l.k1 = 1.0f / l.a;
+  } else {
+    l.a = (float)(m->sigma * 1.414213);
+    l.k1 = (float)(1.0 / ((double)l.a * 1.7724538509055160273));
+  }
+  l.inv_a = 1.0f / l.a;
+  l.offset = (float)m->offset;
+  l.nbins = m->nbounds - 1;
+  return l;
+}
+
+// y / a, correctly rounded but for rare halfway cases (div_lik's form)
+__host__ __device__ __forceinline__ float div_link(float y, const Link& c) {
+  const float q = y * c.inv_a;
+  const float r = __builtin_fmaf(-q, c.a, y);
+  const float f = __builtin_fmaf(r, c.inv_a, q);
+  return (fabsf(q) < 3.0e38f) ? f : q;  // (an infinite edge stays infinite, not NaN)
+}
+
+// exp(-z^2) with the rounding error of z^2 carried along (z^2 = s + e exactly; the argument's
+// error, |z^2| 2^-24, would otherwise be the result's relative error: 1e-6 at |z| = 4)
+__host__ __device__ __forceinline__ float exp_neg_sq(float z) {
+  const float s = z * z;
+  const float e = __builtin_fmaf(z, z, -s);
+  const float E = expf(-s);
+  return __builtin_fmaf(-e, E, E);
+}
+
+// One bin (lo, hi) at x: P, P' and P'' (see the file header).
+template <bool LOGIT>
+__host__ __device__ __forceinline__ void bin_terms(float x, float lo, float hi, const Link& c,
+                                                   float& P, float& P1, float& P2) {
+  const float u = div_link(hi - x, c), w = div_link(lo - x, c);
+  const bool mir = (u + w) > 0.0f;
+  const float uu = mir ? -w : u, ww = mir ? -u : w;  // uu > ww, uu + ww <= 0
+  if (LOGIT) {
+    const bool su = !(fabsf(uu) < kSatLogit), sw = !(fabsf(ww) < kSatLogit);
+    const float Eu = su ? 0.0f : expf(-fabsf(uu)), Ew = sw ? 0.0f : expf(-fabsf(ww));
+    const float ru = 1.0f / (1.0f + Eu), rw = 1.0f / (1.0f + Ew);
+    const float Fu = uu < 0.0f ? Eu * ru : ru, Fw = ww < 0.0f ? Ew * rw : rw;
+    const float fu = Eu * ru * ru, fw = Ew * rw * rw;  // F (1 - F)
+    // (1 - 2F) = +-(1 - E) r
+    const float mu = (uu < 0.0f ? 1.0f : -1.0f) * (1.0f - Eu) * ru;
+    const float mw = (ww < 0.0f ? 1.0f : -1.0f) * (1.0f - Ew) * rw;
+    P = Fu - Fw;
+    const float p1 = -(fu - fw) * c.k1;
+    P1 = mir ? -p1 : p1;
+    P2 = (fu * mu - fw * mw) * (c.k1 * c.k1);
+  } else {
+    const bool su = !(fabsf(uu) < kSatProbit), sw = !(fabsf(ww) < kSatProbit);
+    const float eu = su ? 0.0f : exp_neg_sq(uu), ew = sw ? 0.0f : exp_neg_sq(ww);
+    // F(z) = 0.5 erfc(-z): the lower edge is a tail, the upper one at most 1
+    P = 0.5f * erfcf(-uu) - 0.5f * erfcf(-ww);
+    const float pu = eu * c.k1, pw = ew * c.k1;            // phi
+    const float zu = su ? 0.0f : uu * pu, zw = sw ? 0.0f : ww * pw;  // z phi
+    const float p1 = -(pu - pw);
+    P1 = mir ? -p1 : p1;
+    P2 = -(2.0f * zu - 2.0f * zw) * c.inv_a;
+  }
+}
+
+// curvature of one entry's -log P in t (the map value); code in [0, nbins)
+template <bool LOGIT, bool LOG, int KIND>
+__host__ __device__ __forceinline__ float entry_curvature(float t, int code,
+                                                          const float2* __restrict__ edges,
+                                                          const Link& c) {
+  float x = t, tinv2 = 1.0f;
+  if (LOG) {
+    const float tp = t + c.offset;
+    x = logf(tp);
+    const float ti = 1.0f / tp;
+    tinv2 = ti * ti;
+  }
+  float h;
+  if (KIND == INFO_OBSERVED) {
+    const float2 e = edges[code];
+    float P, P1, P2;
+    bin_terms<LOGIT>(x, e.x, e.y, c, P, P1, P2);
+    const float ip = 1.0f / P;
+    const float gx = -P1 * ip;
+    h = __builtin_fmaf(gx, gx, -P2 * ip);
+    if (LOG) h -= gx;
+    h = (P > 0.0f) ? h : 0.0f;
+  } else {
+    h = 0.0f;
+    for (int b = 0; b < c.nbins; ++b) {
+      const float2 e = edges[b];
+      float P, P1, P2;
+      bin_terms<LOGIT>(x, e.x, e.y, c, P, P1, P2);
+      const float term = P1 * P1 / P;
+      h += (P > 0.0f) ? term : 0.0f;
+    }
+  }
+  return h * tinv2;
+}
+
+// upper-triangle index of (i, j), i <= j, of an N x N symmetric block
+template <int N>
+__host__ __device__ constexpr int tri(int i, int j) {
+  return i * N - (i * (i - 1)) / 2 + (j - i);
+}
+// ... of (i, j) in either order
+template <int N>
+__host__ __device__ constexpr int sym(int i, int j) {
+  return i <= j ? tri<N>(i, j) : tri<N>(j, i);
+}
+
+// pitch (floats) of the C^T table in LDS: a row is RP floats read as 16-byte vectors; the 4-float
+// pad spreads rows over the banks as the passes' tables do
+__host__ __device__ constexpr int info_pitch(int RP) { return RP > 4 ? RP + 4 : 4; }
+
+inline size_t sinfo_lds(int K, int RP, int nbins) {
+  return (size_t)K * info_pitch(RP) * 4 + (size_t)nbins * 8;
+}
+
+template <typename E>
+struct Ent;
+template <>
+struct Ent<uint16_t> {
+  static constexpr int kBits = 12;
+  static constexpr uint32_t kPad = 15;
+};
+template <>
+struct Ent<uint32_t> {
+  static constexpr int kBits = 24;
+  static constexpr uint32_t kPad = 255;
+};
+
+// decode one entry value into (k, code, pad); k and code are clamped into range, out-of-range
+// values read as pads
+template <typename E, bool SR>
+__device__ __forceinline__ void decode(uint32_t v, int K, int Ko, int nbins, int& k, int& code,
+                                       bool& pad) {
+  if (SR) {
+    code = (int)v >= Ko ? 1 : 0;
+    k = (int)v - (code ? Ko : 0);
+    pad = (int)v >= 2 * Ko || k >= K;
+  } else {
+    k = (int)(v & ((1u << Ent<E>::kBits) - 1u));
+    code = (int)(v >> Ent<E>::kBits);
+    pad = (uint32_t)code == Ent<E>::kPad || code >= nbins || k >= K;
+  }
+  k = pad ? 0 : k;
+  code = pad ? 0 : code;
+}
+
+// the lane's two entries (2h, 2h + 1) of chunk `ch` of a slice; a read past the entry array is
+// clamped and returned as pads
+template <typename E>
+__device__ __forceinline__ void load_pair(const E* __restrict__ ent, int64_t idx, int64_t n_ent,
+                                          uint32_t pad_value, uint32_t& v0, uint32_t& v1) {
+  const bool in = idx + 1 < n_ent;
+  const int64_t i = in ? idx : 0;
+  if (sizeof(E) == 2) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(ent + i);  // idx is even: 4-B aligned
+    v0 = w & 0xFFFFu;
+    v1 = w >> 16;
+  } else {
+    const uint2 w = *reinterpret_cast<const uint2*>(ent + i);
+    v0 = w.x;
+    v1 = w.y;
+  }
+  v0 = in ? v0 : pad_value;
+  v1 = in ? v1 : pad_value;
+}
+
+template <int RP, typename E, bool SR, bool LOGIT, bool LOG, int KIND>
+__global__ void __launch_bounds__(kBlock) sinfo_kernel(
+    const E* __restrict__ ent, const int* __restrict__ width, const int64_t* __restrict__ off,
+    int64_t n_ent, int nslices, Link lk, Edges E_, int R, int K, const float* __restrict__ S,
+    const float* __restrict__ C, float* __restrict__ J) {
+  constexpr int CP = info_pitch(RP);
+  constexpr int NT = RP * (RP + 1) / 2;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Cl = smem;                                             // [K][CP]
+  float2* El = reinterpret_cast<float2*>(Cl + (size_t)K * CP);  // [nbins]
+  for (int i = threadIdx.x; i < K * RP; i += kBlock) {
+    const int k = i / RP, r = i - k * RP;
+    Cl[k * CP + r] = r < R ? C[(int64_t)r * K + k] : 0.0f;
+  }
+  for (int b = threadIdx.x; b < lk.nbins; b += kBlock) El[b] = E_.e[b];
+  __syncthreads();
+
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int l = lane & (QSC_SLICE - 1), h = lane >> 5;
+  const int Ko = sr_off(K);
+  const uint32_t pad_value = SR ? 2u * (uint32_t)Ko : (Ent<E>::kPad << Ent<E>::kBits);
+  for (int s = blockIdx.x * kWaves + wave; s < nslices; s += gridDim.x * kWaves) {
+    const int64_t q = (int64_t)s * QSC_SLICE + l;
+    float sv[RP];
+#pragma unroll
+    for (int r = 0; r < RP; r += 4) {
+      const float4 x = *reinterpret_cast<const float4*>(S + q * RP + r);
+      sv[r] = x.x;
+      sv[r + 1] = x.y;
+      sv[r + 2] = x.z;
+      sv[r + 3] = x.w;
+    }
+    float acc[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) acc[i] = 0.0f;
+    const int nch = width[s] >> 2;  // 4-entry chunks of every list of the slice
+    const int64_t base = off[s] + l * 4 + 2 * h;
+    uint32_t n0, n1;
+    load_pair<E>(ent, base, n_ent, pad_value, n0, n1);
+    for (int ch = 0; ch < nch; ++ch) {
+      const uint32_t v[2] = {n0, n1};
+      // the next chunk's entries while this one is worked (past the last list: the next slice's
+      // entries or the array's pad tail, QSC_ENTRY_TAIL; clamped in load_pair either way)
+      load_pair<E>(ent, base + (int64_t)(ch + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0, n1);
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        int k, code;
+        bool pad;
+        decode<E, SR>(v[e], K, Ko, lk.nbins, k, code, pad);
+        float cv[RP];
+#pragma unroll
+        for (int r = 0; r < RP; r += 4) {
+          const float4 x = *reinterpret_cast<const float4*>(Cl + k * CP + r);
+          cv[r] = x.x;
+          cv[r + 1] = x.y;
+          cv[r + 2] = x.z;
+          cv[r + 3] = x.w;
+        }
+        float t = 0.0f;
+#pragma unroll
+        for (int r = 0; r < RP; ++r) t = __builtin_fmaf(sv[r], cv[r], t);
+        float hh = entry_curvature<LOGIT, LOG, KIND>(t, code, El, lk);
+        hh = pad ? 0.0f : hh;  // a pad adds exactly 0 (c_k is finite)
+#pragma unroll
+        for (int i = 0; i < RP; ++i) {
+          const float hi_ = hh * cv[i];
+#pragma unroll
+          for (int j = i; j < RP; ++j)
+            acc[tri<RP>(i, j)] = __builtin_fmaf(hi_, cv[j], acc[tri<RP>(i, j)]);
+        }
+      }
+    }
+    // the two halves' partial blocks (the same bits on both lanes), then each half's rows
+#pragma unroll
+    for (int i = 0; i < NT; ++i) acc[i] += __shfl_xor(acc[i], 32, 64);
+    float* out = J + q * (RP * RP);
+#pragma unroll
+    for (int ii = 0; ii < RP / 2; ++ii) {
+#pragma unroll
+      for (int j = 0; j < RP; j += 4) {
+        // row ii (half 0) or row RP / 2 + ii (half 1), columns j .. j + 3
+        const int i0 = ii, i1 = RP / 2 + ii;
+        const float4 val = make_float4(h ? acc[sym<RP>(i1, j)] : acc[sym<RP>(i0, j)],
+                                       h ? acc[sym<RP>(i1, j + 1)] : acc[sym<RP>(i0, j + 1)],
+                                       h ? acc[sym<RP>(i1, j + 2)] : acc[sym<RP>(i0, j + 2)],
+                                       h ? acc[sym<RP>(i1, j + 3)] : acc[sym<RP>(i0, j + 3)]);
+        *reinterpret_cast<float4*>(out + (h * (RP / 2) + ii) * RP + j) = val;
+      }
+    }
+  }
+}
+
+// elementwise curvature (qsc_entry_info): the device function of the kernel above
+template <bool LOGIT, bool LOG, int KIND>
+__global__ void __launch_bounds__(kBlock) entry_info_kernel(const int64_t* __restrict__ Y,
+                                                            const float* __restrict__ T, int64_t n,
+                                                            Link lk, Edges E_,
+                                                            float* __restrict__ H) {
+  __shared__ float2 se[QSC_MAX_BOUNDS - 1];
+  for (int i = threadIdx.x; i < lk.nbins; i += blockDim.x) se[i] = E_.e[i];
+  __syncthreads();
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t y = Y[i];
+    y = y < 0 ? 0 : (y >= lk.nbins ? lk.nbins - 1 : y);
+    H[i] = entry_curvature<LOGIT, LOG, KIND>(T[i], (int)y, se, lk);
+  }
+}
+
+// One thread per position: Cholesky of J_q + ridge I (rows >= R replaced by the identity), the
+// inverse of the factor in place, then the standard deviations.
+template <int RP>
+__global__ void __launch_bounds__(kBlock) info_std_kernel(
+    const float* __restrict__ J, const int* __restrict__ perm, int R, int P, int Pp,
+    const float* __restrict__ C, int K, float ridge, float* __restrict__ std_S,
+    float* __restrict__ std_T, int* __restrict__ nbad) {
+  const int64_t q = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+  bool bad = false;
+  if (q < Pp) {
+    const int p = perm[q];
+    const bool live = p >= 0 && p < P;
+    float out[RP];
+#pragma unroll
+    for (int i = 0; i < RP; ++i) out[i] = 0.0f;
+    if (live) {
+      // lower triangle a[i][j], j <= i, at tri(j, i)
+      float a[RP * (RP + 1) / 2];
+      const float* Jq = J + q * (RP * RP);
+#pragma unroll
+      for (int i = 0; i < RP; ++i) {
+#pragma unroll
+        for (int j0 = 0; j0 <= i; j0 += 4) {
+          const float4 x = *reinterpret_cast<const float4*>(Jq + i * RP + j0);
+          const float xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int j = j0 + e;
+            if (j <= i) {
+              float v = xs[e];
+              if (j == i) v += ridge;
+              if (i >= R) v = (j == i) ? 1.0f : 0.0f;
+              a[tri<RP>(j, i)] = v;
+            }
+          }
+        }
+      }
+      float dinv[RP];  // 1 / L[i][i]
+#pragma unroll
+      for (int j = 0; j < RP; ++j) {
+        float piv = a[tri<RP>(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) piv = __builtin_fmaf(-a[tri<RP>(k, j)], a[tri<RP>(k, j)], piv);
+        if (!(piv > 0.0f)) {  // (also a NaN block)
+          bad = true;
+          piv = 1.0f;
+        }
+        const float d = sqrtf(piv);
+        dinv[j] = 1.0f / d;
+        a[tri<RP>(j, j)] = d;
+#pragma unroll
+        for (int i = j + 1; i < RP; ++i) {
+          float v = a[tri<RP>(j, i)];
+#pragma unroll
+          for (int k = 0; k < j; ++k) v = __builtin_fmaf(-a[tri<RP>(k, i)], a[tri<RP>(k, j)], v);
+          a[tri<RP>(j, i)] = v * dinv[j];
+        }
+      }
+      // M = L^-1 in place, column by column: M[j][j] = 1 / L[j][j],
+      // M[i][j] = -(sum_{k = j}^{i-1} L[i][k] M[k][j]) / L[i][i]   (columns > j still hold L)
+#pragma unroll
+      for (int j = 0; j < RP; ++j) {
+        a[tri<RP>(j, j)] = dinv[j];
+#pragma unroll
+        for (int i = j + 1; i < RP; ++i) {
+          float v = 0.0f;
+#pragma unroll
+          for (int k = j; k < i; ++k) v = __builtin_fmaf(a[tri<RP>(k, i)], a[tri<RP>(j, k)], v);
+          a[tri<RP>(j, i)] = -v * dinv[i];
+        }
+      }
+      // diag(A^-1)[j] = sum_{i >= j} M[i][j]^2
+#pragma unroll
+      for (int j = 0; j < RP; ++j) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = j; i < RP; ++i) v = __builtin_fmaf(a[tri<RP>(j, i)], a[tri<RP>(j, i)], v);
+        out[j] = j < R ? (bad ? __builtin_inff() : sqrtf(v)) : 0.0f;
+      }
+      if (std_T != nullptr) {
+        for (int k = 0; k < K; ++k) {  // (C[r][k]: the same address on every lane)
+          float ck[RP];
+#pragma unroll
+          for (int r = 0; r < RP; ++r) ck[r] = r < R ? C[(int64_t)r * K + k] : 0.0f;
+          float v = 0.0f;
+#pragma unroll
+          for (int i = 0; i < RP; ++i) {
+            float y = 0.0f;
+#pragma unroll
+            for (int j = 0; j <= i; ++j) y = __builtin_fmaf(a[tri<RP>(j, i)], ck[j], y);
+            v = __builtin_fmaf(y, y, v);
+          }
+          std_T[(int64_t)k * P + p] = bad ? __builtin_inff() : sqrtf(v);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RP; r += 4)
+      *reinterpret_cast<float4*>(std_S + q * RP + r) =
+          make_float4(out[r], out[r + 1], out[r + 2], out[r + 3]);
+  }
+  // one integer atomic per wave (integer addition: any order gives the same count)
+  const unsigned long long m = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && m != 0ull) atomicAdd(nbad, __popcll(m));
+}
+
+int cu_count_info() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+    return 256;
+  return n;
+}
+
+bool info_model_ok(const qsc_model* m) {
+  if (!m || m->nbounds < 2 || m->nbounds > QSC_MAX_BOUNDS || !(m->sigma > 0.0)) return false;
+  if (m->loss != QSC_LOSS_PROBIT && m->loss != QSC_LOSS_LOGIT) return false;
+  return true;
+}
+
+}  // namespace
+
+#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+
+// dispatch over (link, log model, kind) for LAUNCH(LOGIT, LOG, KIND)
+#define QSC_INFO_DISPATCH(LAUNCH)                                        \
+  do {                                                                   \
+    const bool lg_ = m->loss == QSC_LOSS_LOGIT, lo_ = m->log_model != 0; \
+    if (kind == INFO_OBSERVED) {                                         \
+      if (lg_ && lo_) LAUNCH(true, true, INFO_OBSERVED);                 \
+      else if (lg_) LAUNCH(true, false, INFO_OBSERVED);                  \
+      else if (lo_) LAUNCH(false, true, INFO_OBSERVED);                  \
+      else LAUNCH(false, false, INFO_OBSERVED);                          \
+    } else {                                                             \
+      if (lg_ && lo_) LAUNCH(true, true, INFO_EXPECTED);                 \
+      else if (lg_) LAUNCH(true, false, INFO_EXPECTED);                  \
+      else if (lo_) LAUNCH(false, true, INFO_EXPECTED);                  \
+      else LAUNCH(false, false, INFO_EXPECTED);                          \
+    }                                                                    \
+  } while (0)
+
+extern "C" {
+
+QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                      const int64_t* s_off, const qsc_model* m, int32_t R, const float* S,
+                      const float* C, int32_t kind, float* J, void* stream) {
+  if (!d || !s_width || !s_off || !S || !C || !J || !info_model_ok(m)) return QSC_EINVAL;
+  if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
+  if (R < 1 || R > QSC_MAX_R || d->K < 1 || d->P < 1 || d->Pp < d->P || (d->Pp % 64) != 0 ||
+      d->nbins != m->nbounds - 1 || d->s_entries < 0 || (d->s_entries > 0 && !s_entries))
+    return QSC_EINVAL;
+  if (d->rowfmt != 0 && d->rowfmt != 1) return QSC_EINVAL;
+  // signed rows: the one-bit layout, narrow entries, every row index representable
+  if (d->rowfmt == 1 && (d->wide || d->nbins != 2 || (int64_t)sr_rows(d->K) > 0x10000))
+    return QSC_EINVAL;
+  if (!d->wide && d->rowfmt == 0 && (d->K > 4096 || d->nbins > 15)) return QSC_EINVAL;
+  if (d->wide && d->K > (1 << 24)) return QSC_EINVAL;
+  const int RP = qsc_rank_pad(R);
+  const size_t shm = sinfo_lds(d->K, RP, d->nbins);
+  if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
+  const Link lk = make_link(m);
+  Edges E;
+  make_edges(m, &E);
+  const int nslices = d->Pp / QSC_SLICE;
+  // a grid-stride walk over the slices (any grid gives the same bits): enough workgroups to fill
+  // the device, few enough that the C^T staging stays a small part of the traffic
+  const int64_t want = ceil_div(nslices, kWaves);
+  const dim3 grid((unsigned)std::min<int64_t>(want, (int64_t)cu_count_info() * 8)), blk(kBlock);
+  hipStream_t hs = STREAM(stream);
+  const bool sr = d->rowfmt == 1;
+#define SINFO_LAUNCH_E(RPV, ET, SRV, LGT, LOGV, KD)                                              \
+  hipLaunchKernelGGL((sinfo_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,            \
+                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
+                     R, d->K, S, C, J)
+#define SINFO_LAUNCH_RP(RPV, LGT, LOGV, KD)                                  \
+  do {                                                                       \
+    if (sr) {                                                                \
+      /* (signed rows: linear one-bit only) */                               \
+      if (!LOGV) SINFO_LAUNCH_E(RPV, uint16_t, true, LGT, false, KD);        \
+    } else if (d->wide) SINFO_LAUNCH_E(RPV, uint32_t, false, LGT, LOGV, KD); \
+    else SINFO_LAUNCH_E(RPV, uint16_t, false, LGT, LOGV, KD);                \
+  } while (0)
+#define SINFO_LAUNCH(LGT, LOGV, KD)                      \
+  do {                                                   \
+    if (RP == 4) SINFO_LAUNCH_RP(4, LGT, LOGV, KD);      \
+    else if (RP == 8) SINFO_LAUNCH_RP(8, LGT, LOGV, KD); \
+    else SINFO_LAUNCH_RP(16, LGT, LOGV, KD);             \
+  } while (0)
+  if (sr && m->log_model) return QSC_EINVAL;
+  QSC_INFO_DISPATCH(SINFO_LAUNCH);
+#undef SINFO_LAUNCH
+#undef SINFO_LAUNCH_RP
+#undef SINFO_LAUNCH_E
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_info_std(const float* J, const int32_t* perm, int32_t R, int32_t P, int32_t Pp,
+                         const float* C, int32_t K, float ridge, float* std_S, float* std_T,
+                         int32_t* nbad, void* stream) {
+  if (!J || !perm || !std_S || !nbad || R < 1 || R > QSC_MAX_R || P < 1 || Pp < P ||
+      !(ridge >= 0.0f) || (std_T && (!C || K < 1)))
+    return QSC_EINVAL;
+  const int RP = qsc_rank_pad(R);
+  const dim3 grid((unsigned)ceil_div(Pp, kBlock)), blk(kBlock);
+  if (RP == 4)
+    hipLaunchKernelGGL(info_std_kernel<4>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
+                       ridge, std_S, std_T, nbad);
+  else if (RP == 8)
+    hipLaunchKernelGGL(info_std_kernel<8>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
+                       ridge, std_S, std_T, nbad);
+  else
+    hipLaunchKernelGGL(info_std_kernel<16>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
+                       ridge, std_S, std_T, nbad);
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_entry_info(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
+                           int32_t kind, float* H, void* stream) {
+  if (!info_model_ok(m) || n < 0 || (n > 0 && (!Y || !T || !H))) return QSC_EINVAL;
+  if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
+  if (n == 0) return QSC_OK;
+  const Link lk = make_link(m);
+  Edges E;
+  make_edges(m, &E);
+  const int64_t want = ceil_div(n, kBlock);
+  const dim3 grid((unsigned)std::min<int64_t>(want, 8192)), blk(kBlock);
+  hipStream_t hs = STREAM(stream);
+#define ENTRY_LAUNCH(LGT, LOGV, KD) \
+  hipLaunchKernelGGL((entry_info_kernel<LGT, LOGV, KD>), grid, blk, 0, hs, Y, T, n, lk, E, H)
+  QSC_INFO_DISPATCH(ENTRY_LAUNCH);
+#undef ENTRY_LAUNCH
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+}  // extern "C"

@@ -37,6 +37,95 @@ class SolveResult:
     Z: Optional[torch.Tensor] = None
     iters: int = 0
     fused: bool = False                 # S-step + next C-pass ran as one launch (qsc_scpass)
+    std_S: Optional[torch.Tensor] = None  # (R, 1, I, J) standard deviations (solve(confidence=...))
+    unidentified: Optional[int] = None  # pixels whose information block is not positive definite
+
+
+@dataclass
+class ConfidenceResult:
+    std_S: torch.Tensor                 # (R, 1, I, J), pixel order; +inf where unidentified
+    std_T: Optional[torch.Tensor]       # (K, 1, I, J) or None (map_std=False)
+    info: torch.Tensor                  # (P, R, R) information blocks J_p, pixel order
+    unidentified: int                   # pixels whose J_p + ridge I is not positive definite
+
+
+INFO_KINDS = {"expected": 0, "observed": 1}  # QSC_INFO_EXPECTED, QSC_INFO_OBSERVED
+
+
+def check_confidence(kind, ridge, loss):
+    """Validate the confidence arguments (before anything touches a device)."""
+    if kind not in INFO_KINDS:
+        raise ValueError("confidence kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    if ridge is not None and not float(ridge) >= 0.0:
+        raise ValueError("the confidence ridge must be >= 0, got %r" % (ridge,))
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: it has no Fisher information')
+
+
+def _confidence_pos(obs, S_pos, C, R, kind, ridge, map_std):
+    """confidence() on a position-order S (Pp, RP) and a device C (R, K)."""
+    desc, s_entries, _ = obs.layout(R)
+    RP = obs.rank_pad(R)
+    dev = S_pos.device
+    J = torch.empty((obs.Pp, RP, RP), dtype=torch.float32, device=dev)
+    _lib.call("qsc_sinfo", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
+              obs.model, R, _lib.ptr(S_pos), _lib.ptr(C), INFO_KINDS[kind], _lib.ptr(J),
+              _lib.stream())
+    std_pos = torch.empty((obs.Pp, RP), dtype=torch.float32, device=dev)
+    std_T = torch.empty((obs.K, obs.P), dtype=torch.float32, device=dev) if map_std else None
+    nbad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("qsc_info_std", _lib.ptr(J), _lib.ptr(obs.perm), R, obs.P, obs.Pp, _lib.ptr(C),
+              obs.K, float(ridge), _lib.ptr(std_pos), _lib.ptr(std_T), _lib.ptr(nbad),
+              _lib.stream())
+    std_S = obs.to_pixels(std_pos, R).reshape(R, 1, obs.I, obs.J)
+    info = J[obs.iperm().long()][:, :R, :R].contiguous()
+    if std_T is not None:
+        std_T = std_T.reshape(obs.K, 1, obs.I, obs.J)
+    return ConfidenceResult(std_S=std_S, std_T=std_T, info=info, unidentified=int(nbad.item()))
+
+
+def confidence(obs, S, C, kind="expected", ridge=0.0, map_std=False):
+    """Laplace / Cramer-Rao confidence of the loss fields S and of the map at (S, C).
+
+    Conditional on C, the Hessian of the NLL in S is block diagonal: pixel p has the R x R block
+    J_p = sum_{k observed at p} h(k, p) c_k c_k^T, c_k = C[:, k], with h the curvature of one
+    entry's -log P in T_hat[k, p] (include/qsc.h, qsc_sinfo, has the formulas).  kind="expected"
+    takes the Fisher information of each entry (independent of the observed code, J_p >= 0: the
+    Cramer-Rao bound); kind="observed" the curvature at the observed code (the Hessian a double
+    backward of the NLL gives; under the log model it may be indefinite).  Then
+      std_S[r, p] = sqrt(((J_p + ridge I)^-1)[r, r]),
+      std_T[k, p] = sqrt(c_k^T (J_p + ridge I)^-1 c_k)   (map_std=True; delta method, for every
+                    map entry, observed or not).
+    A pixel whose J_p + ridge I is not positive definite (no observations and ridge = 0, say) is
+    unidentified: its standard deviations are +inf and it is counted in `unidentified`.
+    C is treated as known -- its R K parameters are informed by all observations, a pixel's R
+    values of S by that pixel's few -- so the C-side information and the S-C covariance are not
+    included: the figures are lower bounds on the joint uncertainty.
+    obs: the Observations the solve ran on; S (R,1,I,J) or (R,P), C (R,K).  Returns a
+    ConfidenceResult(std_S (R,1,I,J), std_T (K,1,I,J) or None, info (P,R,R), unidentified).
+    Raises ValueError for an unknown kind, ridge < 0 or obs.loss == "squared"."""
+    check_confidence(kind, ridge, getattr(obs, "loss", None))
+    R = S.shape[0]
+    S_pos = obs.to_positions(S.reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    return _confidence_pos(obs, S_pos, Cd, R, kind, ridge, map_std)
+
+
+def default_confidence_ridge(S, lambda_s):
+    """lambda_s / ||S||_F: the isotropic part of the Hessian of the solver's lambda_s ||S||_F
+    regulariser, (lambda_s / ||S||) (I - s s^T / ||S||^2) with s = vec(S); its rank-one part
+    couples all pixels and is dropped.  0 for S = 0."""
+    n = float(torch.linalg.norm(S.detach().to(torch.float32)))
+    return float(lambda_s) / n if n > 0.0 else 0.0
+
+
+def _attach_confidence(res, obs, confidence_kind, confidence_ridge, lambda_s):
+    """solve(confidence=...): std_S and unidentified of the returned S, C."""
+    ridge = (default_confidence_ridge(res.S, lambda_s) if confidence_ridge is None
+             else float(confidence_ridge))
+    c = confidence(obs, res.S, res.C, kind=confidence_kind, ridge=ridge)
+    res.std_S, res.unidentified = c.std_S, c.unidentified
+    return res
 
 
 # Longest run captured as one hipGraph; longer runs replay several (results are identical:
@@ -492,7 +581,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           restart=False, restart_samples=(200, 200), T_true=None, nmse_every=0,
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
-          smooth=0.0, smooth_kind="quad", smooth_delta=None):
+          smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
+          confidence_ridge=None):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -530,12 +620,26 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     Raises ValueError for smooth < 0, an unknown kind, huber without delta > 0, or smooth > 0
     with a generator (which is itself the prior).  smooth = 0 (default) is the unregularised
     path, unchanged.
+    confidence="expected" | "observed" (free S and holdout solves; not in the reference): the
+    result gains std_S (R,1,I,J), the per-pixel standard deviations of the returned S from the
+    Fisher information conditional on C, and `unidentified` (see qmc.confidence, which also
+    gives the map's standard deviations).  The ridge added to every pixel's information block is
+    confidence_ridge, or by default lambda_s / ||S||_F: the isotropic part of the Hessian of the
+    lambda_s ||S||_F regulariser (its rank-one part, -lambda_s s s^T / ||S||^3, couples all
+    pixels and is dropped).  Raises ValueError with a generator (the generator is the prior and
+    S is not free), with loss="squared", for an unknown kind or a negative ridge.  The default
+    None leaves every path and result as it is.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
     smooth = check_smooth(smooth, smooth_kind, smooth_delta)
     if smooth > 0.0 and generator is not None:
         raise ValueError("smooth > 0 applies to free S only: a generator already carries the "
                          "spatial prior")
+    if confidence is not None:
+        check_confidence(confidence, confidence_ridge, obs.loss if obs is not None else loss)
+        if generator is not None:
+            raise ValueError("confidence applies to free S only: with a generator S is not a "
+                             "free parameter (the generator is the prior)")
     if log_model and obs is None:
         # the reference log model's default offset (qmc/quantization_model_log.py:7, 9)
         offset = LOG_OFFSET if offset is None else float(offset)
@@ -564,9 +668,12 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     if C_init is None:
         C_init = torch.zeros(R, K)
     if generator is None and obs_h is not None:
-        return _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
-                              max_iter, betas, eps, project_c, fuse, project_s, use_graph,
-                              int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
+        res = _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
+                             max_iter, betas, eps, project_c, fuse, project_s, use_graph,
+                             int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
+        if confidence is not None:  # (on the fitted entries, the held-out ones excluded)
+            _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
+        return res
     if generator is None:
         if S_init is None:
             S_init = torch.zeros(R, 1, I, J)
@@ -592,8 +699,11 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
                 callback(done, sol)
         nmse = sol.nmse_history()
         costs_c, costs_s = sol.history()
-        return SolveResult(S=sol.S_pixels(), C=sol.C.clone(), costs_c=costs_c, costs_s=costs_s,
-                           nmse=nmse, iters=max_iter, fused=sol.fuse)
+        res = SolveResult(S=sol.S_pixels(), C=sol.C.clone(), costs_c=costs_c, costs_s=costs_s,
+                          nmse=nmse, iters=max_iter, fused=sol.fuse)
+        if confidence is not None:
+            _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
+        return res
     return _solve_generator(obs, generator, Z_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
                             max_iter, betas, eps, project_c, restart, restart_samples, T_true,
                             nmse_every, callback, use_graph=use_graph)

@@ -88,3 +88,30 @@ def smooth_penalty(S, kind="quad", delta=None):
     loss fields S (R,1,I,J) on the GPU -- fused.smooth_penalty (the solver's own HIP kernel)."""
     from .fused import smooth_penalty as _sp
     return _sp(S, kind, delta)
+
+
+def entry_information(T_hat, Y, bin_boundaries, noise_std, offset=0.0, log_model=False,
+                      loss="probit", kind="expected"):
+    """Elementwise curvature h of -log P(Y | T_hat) in the map value T_hat, the per-entry weight
+    of the information blocks of qmc.confidence (J_p = sum_k h c_k c_k^T), on the HIP op
+    qsc_entry_info (the device function of qsc_sinfo; formulas in include/qsc.h).
+
+    T_hat holds map values t (not the model-domain x of prob_probit): under the log model
+    x = log(t + offset) and the chain rule is applied.  kind="observed": the second derivative at
+    the code Y (it may be negative under the log model); kind="expected": the Fisher information
+    sum_b (dP_b/dt)^2 / P_b, independent of Y and >= 0.  loss is "probit" or "logit" (noise_std
+    then the logistic scale).  Returns a float32 tensor shaped like T_hat on T_hat's device."""
+    from . import _lib
+    from ._model import _dev
+    from .qmc import check_confidence, INFO_KINDS
+    check_confidence(kind, None, loss)
+    m = _lib.make_model(bin_boundaries, noise_std, offset if log_model else 0.0, log_model,
+                        loss=loss)
+    Td = _dev(T_hat.detach().to(torch.float32))
+    Yd = _dev(Y.to(torch.int64))
+    Yd, Td = torch.broadcast_tensors(Yd, Td)
+    Yd, Td = Yd.contiguous(), Td.contiguous()
+    H = torch.empty(Td.shape, dtype=torch.float32, device=Td.device)
+    _lib.call("qsc_entry_info", _lib.ptr(Yd), _lib.ptr(Td), Td.numel(), m, INFO_KINDS[kind],
+              _lib.ptr(H), _lib.stream())
+    return H if T_hat.is_cuda else H.to(T_hat.device)
