@@ -533,6 +533,61 @@ QSC_API int qsc_info_std(const float* J, const int32_t* perm, int32_t R, int32_t
 QSC_API int qsc_entry_info(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
                            int32_t kind, float* H, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-pixel damped Newton / Fisher-scoring fit of the loss fields for known spectra (qsc_sfit.hip).
+ *   Conditional on C the likelihood separates over positions.  Position q minimises over
+ *   s = S[q][0..R)
+ *     f_q(s) = sum_{entries (k, code) of q} -log max(P(code | t = s . c_k), FLT_MIN)
+ *              + ridge / 2 |s|^2
+ *   with P, the edges, the log-model chain and the saturation rules of qsc_sinfo above (convex in
+ *   the linear model: both links are log-concave).  Per entry f += -log max(P, FLT_MIN),
+ *   g += g_t c_k with g_t = -P'/P dx/dt, J += h c_k c_k^T with h the entry curvature of `kind`
+ *   (QSC_INFO_OBSERVED: Newton; QSC_INFO_EXPECTED: Fisher scoring, J >= 0).  A pad entry adds
+ *   exactly 0; an entry with P == 0 adds 0 to g, J and -log FLT_MIN to f; in the log model an
+ *   entry with t + offset <= 0 makes f_q = +inf (such a trial point is rejected).
+ *   One launch runs, per position (two lanes; the walk of qsc_sinfo):
+ *     evaluate (f, g, J) at s = S_init[q];  mu = mu0
+ *     repeat up to max_steps times:
+ *       solve (J + (ridge + mu) I) delta = g + ridge s   (Cholesky in registers)
+ *       s' = s - delta;  project != 0: s' = max(s', 0)
+ *       a pivot that is not positive: the step counts as rejected
+ *       evaluate (f', g', J') at s'
+ *       accept iff f' <= f and f' is finite: s <- s', mu <- max(mu / 10, mu0 == 0 ? 0 : mu_min)
+ *       else mu <- max(10 mu, mu_min)                                      mu_min = 1e-6
+ *       converged once an accepted step has |s' - s|_inf <= tol (1 + |s|_inf)
+ *   A converged position stops changing; a wave ends when all its positions have converged.
+ *   f is evaluated in fp64 (from the fp32 s, C and edges) so that the accept test resolves the
+ *   decreases |g|^2 / lambda of the last steps; g and J are fp32.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of workspace qsc_sfit needs for this layout and rank: 0 for R <= 8 (the state before a
+ * trial step stays in registers); for R > 8 one row of the accepted (g, J) per lane of the grid
+ * (at most a few tens of MB, independent of P beyond that). */
+QSC_API size_t qsc_sfit_workspace_bytes(const qsc_obs_desc* d, int32_t R);
+/* S_out[Pp][RP] (position order, RP = qsc_rank_pad(R); rows >= R and padding positions zero;
+ * S_out may alias S_init) = the iteration above from S_init[Pp][RP], over the S-format lists of
+ * any layout qsc_obs_fill produces; perm[Pp] as qsc_info_std (perm[q] < 0: a padding position);
+ * C [R][K].  f_out[Pp] (nullable): the final f_q, ridge term included (0 for padding);
+ * steps[Pp] (nullable, int32): the trial evaluations the position used (<= max_steps; the
+ * evaluation at S_init is not counted).  *n_unconverged, *n_unidentified: device int32 counters
+ * the caller zeroes, each incremented by one integer atomic per wave:
+ *   n_unconverged   positions that had not converged after max_steps;
+ *   n_unidentified  positions where, at every step, a pivot p of J + (ridge + mu) I had p <= mu,
+ *                   i.e. J + ridge I itself had no positive pivot there (for mu = 0: the pivot
+ *                   was not positive at every step) -- no observations and ridge = 0, say; such
+ *                   a position returns S_init unchanged (its g is 0).
+ * Padding positions are never counted.  Every sum is in list order -- no floating-point atomics;
+ * two calls agree bit for bit.  Stream-ordered, never allocates, capturable into a hipGraph.
+ * QSC_EINVAL for m->loss == QSC_LOSS_SQUARED, ridge < 0, mu0 < 0, tol <= 0, max_steps < 1, an
+ * unknown kind, a layout / model mismatch or a workspace smaller than
+ * qsc_sfit_workspace_bytes; QSC_EUNSUPPORTED when C^T and the edges exceed the 160 KiB of LDS
+ * (qsc_sinfo's rule). */
+QSC_API int qsc_sfit(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                     const int64_t* s_off, const int32_t* perm, const qsc_model* m, int32_t R,
+                     const float* C, const float* S_init, int32_t kind, float ridge, float mu0,
+                     float tol, int32_t max_steps, int32_t project, float* S_out, float* f_out,
+                     int32_t* steps, int32_t* n_unconverged, int32_t* n_unidentified, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* debug builds (QSC_DEBUG=1, _build.py --debug): the last failed bounds check in the pass
  * kernels (entry offsets, gather-table rows, lane bins; a failed check is recorded and its index
  * clamped, never trapped) as file id * 100000 + source line, 0 if none, -1 in release builds,

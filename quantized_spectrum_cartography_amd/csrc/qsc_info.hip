@@ -36,195 +36,13 @@
 #include <algorithm>
 
 #include "qsc_common.cuh"
+#include "qsc_info.cuh"
 
 namespace {
 using namespace qsc;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-constexpr size_t kInfoLdsMax = 160 * 1024;  // the LDS of one CU, as the passes' bound
-constexpr float kSatProbit = 14.0f;   // exp(-z^2) == 0 in fp32 from |z| = 10.2 on
-constexpr float kSatLogit = 100.0f;   // exp(-|z|) is denormal from |z| = 87.3 on
-
-enum { INFO_EXPECTED = QSC_INFO_EXPECTED, INFO_OBSERVED = QSC_INFO_OBSERVED };
-
-// per-call constants of the link
-struct Link {
-  float a, inv_a;  // probit: fp32(sigma * 1.414213); logit: the scale s
-  float k1;        // probit: 1 / (a sqrt(pi));  logit: 1 / s
-  float offset;
-  int nbins;
-};
-
-inline Link make_link(const qsc_model* m) {
-  Link l;
-  if (m->loss == QSC_LOSS_LOGIT) {
-    l.a = (float)m->sigma;
-    l.k1 = 1.0f / l.a;
-  } else {
-    l.a = (float)(m->sigma * 1.414213);
-    l.k1 = (float)(1.0 / ((double)l.a * 1.7724538509055160273));
-  }
-  l.inv_a = 1.0f / l.a;
-  l.offset = (float)m->offset;
-  l.nbins = m->nbounds - 1;
-  return l;
-}
-
-// y / a, correctly rounded but for rare halfway cases (div_lik's form)
-__host__ __device__ __forceinline__ float div_link(float y, const Link& c) {
-  const float q = y * c.inv_a;
-  const float r = __builtin_fmaf(-q, c.a, y);
-  const float f = __builtin_fmaf(r, c.inv_a, q);
-  return (fabsf(q) < 3.0e38f) ? f : q;  // (an infinite edge stays infinite, not NaN)
-}
-
-// exp(-z^2) with the rounding error of z^2 carried along (z^2 = s + e exactly; the argument's
-// error, |z^2| 2^-24, would otherwise be the result's relative error: 1e-6 at |z| = 4)
-__host__ __device__ __forceinline__ float exp_neg_sq(float z) {
-  const float s = z * z;
-  const float e = __builtin_fmaf(z, z, -s);
-  const float E = expf(-s);
-  return __builtin_fmaf(-e, E, E);
-}
-
-// One bin (lo, hi) at x: P, P' and P'' (see the file header).
-template <bool LOGIT>
-__host__ __device__ __forceinline__ void bin_terms(float x, float lo, float hi, const Link& c,
-                                                   float& P, float& P1, float& P2) {
-  const float u = div_link(hi - x, c), w = div_link(lo - x, c);
-  const bool mir = (u + w) > 0.0f;
-  const float uu = mir ? -w : u, ww = mir ? -u : w;  // uu > ww, uu + ww <= 0
-  if (LOGIT) {
-    const bool su = !(fabsf(uu) < kSatLogit), sw = !(fabsf(ww) < kSatLogit);
-    const float Eu = su ? 0.0f : expf(-fabsf(uu)), Ew = sw ? 0.0f : expf(-fabsf(ww));
-    const float ru = 1.0f / (1.0f + Eu), rw = 1.0f / (1.0f + Ew);
-    const float Fu = uu < 0.0f ? Eu * ru : ru, Fw = ww < 0.0f ? Ew * rw : rw;
-    const float fu = Eu * ru * ru, fw = Ew * rw * rw;  // F (1 - F)
-    // (1 - 2F) = +-(1 - E) r
-    const float mu = (uu < 0.0f ? 1.0f : -1.0f) * (1.0f - Eu) * ru;
-    const float mw = (ww < 0.0f ? 1.0f : -1.0f) * (1.0f - Ew) * rw;
-    P = Fu - Fw;
-    const float p1 = -(fu - fw) * c.k1;
-    P1 = mir ? -p1 : p1;
-    P2 = (fu * mu - fw * mw) * (c.k1 * c.k1);
-  } else {
-    const bool su = !(fabsf(uu) < kSatProbit), sw = !(fabsf(ww) < kSatProbit);
-    const float eu = su ? 0.0f : exp_neg_sq(uu), ew = sw ? 0.0f : exp_neg_sq(ww);
-    // F(z) = 0.5 erfc(-z): the lower edge is a tail, the upper one at most 1
-    P = 0.5f * erfcf(-uu) - 0.5f * erfcf(-ww);
-    const float pu = eu * c.k1, pw = ew * c.k1;            // phi
-    const float zu = su ? 0.0f : uu * pu, zw = sw ? 0.0f : ww * pw;  // z phi
-    const float p1 = -(pu - pw);
-    P1 = mir ? -p1 : p1;
-    P2 = -(2.0f * zu - 2.0f * zw) * c.inv_a;
-  }
-}
-
-// curvature of one entry's -log P in t (the map value); code in [0, nbins)
-template <bool LOGIT, bool LOG, int KIND>
-__host__ __device__ __forceinline__ float entry_curvature(float t, int code,
-                                                          const float2* __restrict__ edges,
-                                                          const Link& c) {
-  float x = t, tinv2 = 1.0f;
-  if (LOG) {
-    const float tp = t + c.offset;
-    x = logf(tp);
-    const float ti = 1.0f / tp;
-    tinv2 = ti * ti;
-  }
-  float h;
-  if (KIND == INFO_OBSERVED) {
-    const float2 e = edges[code];
-    float P, P1, P2;
-    bin_terms<LOGIT>(x, e.x, e.y, c, P, P1, P2);
-    const float ip = 1.0f / P;
-    const float gx = -P1 * ip;
-    h = __builtin_fmaf(gx, gx, -P2 * ip);
-    if (LOG) h -= gx;
-    h = (P > 0.0f) ? h : 0.0f;
-  } else {
-    h = 0.0f;
-    for (int b = 0; b < c.nbins; ++b) {
-      const float2 e = edges[b];
-      float P, P1, P2;
-      bin_terms<LOGIT>(x, e.x, e.y, c, P, P1, P2);
-      const float term = P1 * P1 / P;
-      h += (P > 0.0f) ? term : 0.0f;
-    }
-  }
-  return h * tinv2;
-}
-
-// upper-triangle index of (i, j), i <= j, of an N x N symmetric block
-template <int N>
-__host__ __device__ constexpr int tri(int i, int j) {
-  return i * N - (i * (i - 1)) / 2 + (j - i);
-}
-// ... of (i, j) in either order
-template <int N>
-__host__ __device__ constexpr int sym(int i, int j) {
-  return i <= j ? tri<N>(i, j) : tri<N>(j, i);
-}
-
-// pitch (floats) of the C^T table in LDS: a row is RP floats read as 16-byte vectors; the 4-float
-// pad spreads rows over the banks as the passes' tables do
-__host__ __device__ constexpr int info_pitch(int RP) { return RP > 4 ? RP + 4 : 4; }
-
-inline size_t sinfo_lds(int K, int RP, int nbins) {
-  return (size_t)K * info_pitch(RP) * 4 + (size_t)nbins * 8;
-}
-
-template <typename E>
-struct Ent;
-template <>
-struct Ent<uint16_t> {
-  static constexpr int kBits = 12;
-  static constexpr uint32_t kPad = 15;
-};
-template <>
-struct Ent<uint32_t> {
-  static constexpr int kBits = 24;
-  static constexpr uint32_t kPad = 255;
-};
-
-// decode one entry value into (k, code, pad); k and code are clamped into range, out-of-range
-// values read as pads
-template <typename E, bool SR>
-__device__ __forceinline__ void decode(uint32_t v, int K, int Ko, int nbins, int& k, int& code,
-                                       bool& pad) {
-  if (SR) {
-    code = (int)v >= Ko ? 1 : 0;
-    k = (int)v - (code ? Ko : 0);
-    pad = (int)v >= 2 * Ko || k >= K;
-  } else {
-    k = (int)(v & ((1u << Ent<E>::kBits) - 1u));
-    code = (int)(v >> Ent<E>::kBits);
-    pad = (uint32_t)code == Ent<E>::kPad || code >= nbins || k >= K;
-  }
-  k = pad ? 0 : k;
-  code = pad ? 0 : code;
-}
-
-// the lane's two entries (2h, 2h + 1) of chunk `ch` of a slice; a read past the entry array is
-// clamped and returned as pads
-template <typename E>
-__device__ __forceinline__ void load_pair(const E* __restrict__ ent, int64_t idx, int64_t n_ent,
-                                          uint32_t pad_value, uint32_t& v0, uint32_t& v1) {
-  const bool in = idx + 1 < n_ent;
-  const int64_t i = in ? idx : 0;
-  if (sizeof(E) == 2) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(ent + i);  // idx is even: 4-B aligned
-    v0 = w & 0xFFFFu;
-    v1 = w >> 16;
-  } else {
-    const uint2 w = *reinterpret_cast<const uint2*>(ent + i);
-    v0 = w.x;
-    v1 = w.y;
-  }
-  v0 = in ? v0 : pad_value;
-  v1 = in ? v1 : pad_value;
-}
 
 template <int RP, typename E, bool SR, bool LOGIT, bool LOG, int KIND>
 __global__ void __launch_bounds__(kBlock) sinfo_kernel(
@@ -449,32 +267,9 @@ int cu_count_info() {
   return n;
 }
 
-bool info_model_ok(const qsc_model* m) {
-  if (!m || m->nbounds < 2 || m->nbounds > QSC_MAX_BOUNDS || !(m->sigma > 0.0)) return false;
-  if (m->loss != QSC_LOSS_PROBIT && m->loss != QSC_LOSS_LOGIT) return false;
-  return true;
-}
-
 }  // namespace
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
-// dispatch over (link, log model, kind) for LAUNCH(LOGIT, LOG, KIND)
-#define QSC_INFO_DISPATCH(LAUNCH)                                        \
-  do {                                                                   \
-    const bool lg_ = m->loss == QSC_LOSS_LOGIT, lo_ = m->log_model != 0; \
-    if (kind == INFO_OBSERVED) {                                         \
-      if (lg_ && lo_) LAUNCH(true, true, INFO_OBSERVED);                 \
-      else if (lg_) LAUNCH(true, false, INFO_OBSERVED);                  \
-      else if (lo_) LAUNCH(false, true, INFO_OBSERVED);                  \
-      else LAUNCH(false, false, INFO_OBSERVED);                          \
-    } else {                                                             \
-      if (lg_ && lo_) LAUNCH(true, true, INFO_EXPECTED);                 \
-      else if (lg_) LAUNCH(true, false, INFO_EXPECTED);                  \
-      else if (lo_) LAUNCH(false, true, INFO_EXPECTED);                  \
-      else LAUNCH(false, false, INFO_EXPECTED);                          \
-    }                                                                    \
-  } while (0)
 
 extern "C" {
 

@@ -39,6 +39,7 @@ class SolveResult:
     fused: bool = False                 # S-step + next C-pass ran as one launch (qsc_scpass)
     std_S: Optional[torch.Tensor] = None  # (R, 1, I, J) standard deviations (solve(confidence=...))
     unidentified: Optional[int] = None  # pixels whose information block is not positive definite
+    polish: Optional["FitSResult"] = None  # solve(polish_s=n): the fit_S run on S (without S)
 
 
 @dataclass
@@ -125,6 +126,121 @@ def _attach_confidence(res, obs, confidence_kind, confidence_ridge, lambda_s):
              else float(confidence_ridge))
     c = confidence(obs, res.S, res.C, kind=confidence_kind, ridge=ridge)
     res.std_S, res.unidentified = c.std_S, c.unidentified
+    return res
+
+
+@dataclass
+class FitSResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J), pixel order (None in SolveResult.polish)
+    nll: float                          # -sum log P at S over the observed entries (no ridge term)
+    steps: torch.Tensor                 # (I, J) int32: trial evaluations each pixel used
+    unconverged: int                    # pixels not converged within max_steps
+    unidentified: int                   # pixels whose J_p + ridge I never had positive pivots
+
+
+def check_fit_s(loss, ridge, kind, max_steps, tol, mu0):
+    """Validate the fit_S arguments (before anything touches a device)."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: fit_S has nothing to fit')
+    if kind is not None and kind not in INFO_KINDS:
+        raise ValueError("fit_S kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    if not float(ridge) >= 0.0:
+        raise ValueError("the fit_S ridge must be >= 0, got %r" % (ridge,))
+    if not float(mu0) >= 0.0:
+        raise ValueError("mu0 must be >= 0, got %r" % (mu0,))
+    if not float(tol) > 0.0:
+        raise ValueError("tol must be > 0, got %r" % (tol,))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1, got %r" % (max_steps,))
+
+
+def _fit_s_pos(obs, S_pos, C, R, kind, ridge, max_steps, tol, mu0, project, S_out=None):
+    """qsc_sfit on a position-order S (Pp, RP) and a device C (R, K): (S_out, f (Pp,),
+    steps (Pp,) int32, counters (2,) int32: unconverged, unidentified), all on the device."""
+    desc, s_entries, _ = obs.layout(R)
+    dev = S_pos.device
+    if S_out is None:
+        S_out = torch.empty_like(S_pos)
+    f = torch.empty(obs.Pp, dtype=torch.float32, device=dev)
+    steps = torch.empty(obs.Pp, dtype=torch.int32, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_sfit_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    _lib.call("qsc_sfit", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
+              _lib.ptr(obs.perm), obs.model, R, _lib.ptr(C), _lib.ptr(S_pos), INFO_KINDS[kind],
+              float(ridge), float(mu0), float(tol), int(max_steps), 1 if project else 0,
+              _lib.ptr(S_out), _lib.ptr(f), _lib.ptr(steps), _lib.ptr(counters[0:1]),
+              _lib.ptr(counters[1:2]), _lib.ptr(ws), nws, _lib.stream())
+    return S_out, f, steps, counters
+
+
+def fit_S(obs, C, S_init=None, ridge=0.0, kind=None, max_steps=30, tol=1e-5, mu0=1e-3,
+          project=None):
+    """The loss fields S for known spectra C: per pixel, a damped Newton / Fisher-scoring fit.
+
+    Given C the likelihood separates over pixels; pixel p minimises
+      f_p(s) = sum_{k observed at p} -log P(Y[k, p] | s . c_k) + ridge / 2 |s|^2,
+    convex under the linear model (both links are log-concave).  One HIP launch (qsc_sfit,
+    include/qsc.h has the iteration) evaluates f, its gradient and the R x R curvature block of
+    every pixel from the packed lists, solves (J + (ridge + mu) I) delta = g + ridge s in
+    registers, accepts the step when f does not increase (else raises the damping mu), and
+    repeats until |delta|_inf <= tol (1 + |s|_inf) or max_steps -- a handful of steps where the
+    alternating solver's Adam S-step needs hundreds.  The point it returns is the conditional MLE
+    (MAP with the ridge) that qmc.confidence's standard deviations are defined at.
+    obs: the Observations; C (R, K) from an earlier solve, spa / gram.nnls_spectra or a
+    catalogue.  S_init (R,1,I,J) or (R,P): default zeros (linear model) or ones (log model).
+    kind "observed" (Newton; default for the linear model) or "expected" (Fisher scoring, always
+    positive semidefinite; default for the log model, whose observed Hessian may be indefinite).
+    project: keep S >= 0 (default: obs.log_model, as solve's project_s).  mu0: initial damping
+    (0: pure Newton steps while they are accepted).
+    Returns FitSResult(S (R,1,I,J), nll, steps (I,J), unconverged, unidentified): nll is the NLL
+    at S without the ridge term, summed in fp64 in a fixed order; unidentified counts pixels
+    whose J_p + ridge I never had all pivots positive (no observations and ridge = 0: such a
+    pixel keeps S_init).  Raises ValueError for loss="squared", negative ridge / mu0, tol <= 0,
+    max_steps < 1 or an unknown kind, before any GPU call."""
+    check_fit_s(getattr(obs, "loss", None), ridge, kind, max_steps, tol, mu0)
+    log_model = bool(getattr(obs, "log_model", False))
+    if kind is None:
+        kind = "expected" if log_model else "observed"
+    if project is None:
+        project = log_model
+    R = C.shape[0]
+    if S_init is None:
+        S_init = (torch.ones if log_model else torch.zeros)(R, obs.P)
+    S_pos = obs.to_positions(S_init.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    S_out, f, steps, counters = _fit_s_pos(obs, S_pos, Cd, R, kind, ridge, max_steps, tol, mu0,
+                                           project)
+    nll = float(f.double().sum() - 0.5 * float(ridge) * (S_out.double() ** 2).sum())
+    unconverged, unidentified = counters.tolist()
+    return FitSResult(S=obs.to_pixels(S_out, R).reshape(R, 1, obs.I, obs.J), nll=nll,
+                      steps=steps[obs.iperm().long()].reshape(obs.I, obs.J),
+                      unconverged=unconverged, unidentified=unidentified)
+
+
+def check_polish(polish_s, generator, loss, smooth):
+    """Validate solve(polish_s=...) (before anything touches a device); the step count."""
+    n = int(polish_s)
+    if n < 0:
+        raise ValueError("polish_s must be >= 0, got %r" % (polish_s,))
+    if n > 0:
+        if generator is not None:
+            raise ValueError("polish_s applies to free S only: with a generator S is not a free "
+                             "parameter")
+        if loss == "squared":
+            raise ValueError('polish_s needs a likelihood: loss="squared" has none')
+        if smooth > 0.0:
+            raise ValueError("polish_s fits every pixel on its own; the smoothness prior "
+                             "(smooth > 0) couples pixels")
+    return n
+
+
+def _polish(res, obs, n, lambda_s, project_s):
+    """solve(polish_s=n): S <- fit_S from the returned S at the returned C."""
+    r = fit_S(obs, res.C, S_init=res.S, ridge=default_confidence_ridge(res.S, lambda_s),
+              max_steps=n, project=project_s)
+    res.S, r.S = r.S, None
+    res.polish = r
     return res
 
 
@@ -582,7 +698,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
-          confidence_ridge=None):
+          confidence_ridge=None, polish_s=0):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -629,12 +745,21 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     pixels and is dropped).  Raises ValueError with a generator (the generator is the prior and
     S is not free), with loss="squared", for an unknown kind or a negative ridge.  The default
     None leaves every path and result as it is.
+    polish_s=n > 0 (free S and holdout solves; not in the reference): after the loop -- and after
+    the holdout's best-check restore -- S is replaced by qmc.fit_S started from it at the returned
+    C, for up to n damped Newton steps per pixel, with the ridge lambda_s / ||S||_F of
+    default_confidence_ridge: the conditional MLE, where the Adam iterate is not stationary in S.
+    It runs before confidence= is attached, so std_S is evaluated at the point the theory is
+    about; result.polish is the FitSResult (without S).  Raises ValueError with a generator, with
+    loss="squared" and with smooth > 0: the fit treats every pixel on its own, and the
+    smoothness prior couples pixels.  The default 0 leaves every path and result bit-identical.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
     smooth = check_smooth(smooth, smooth_kind, smooth_delta)
     if smooth > 0.0 and generator is not None:
         raise ValueError("smooth > 0 applies to free S only: a generator already carries the "
                          "spatial prior")
+    polish_s = check_polish(polish_s, generator, obs.loss if obs is not None else loss, smooth)
     if confidence is not None:
         check_confidence(confidence, confidence_ridge, obs.loss if obs is not None else loss)
         if generator is not None:
@@ -671,6 +796,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         res = _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
                              max_iter, betas, eps, project_c, fuse, project_s, use_graph,
                              int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
+        if polish_s:
+            _polish(res, obs, polish_s, lambda_s, project_s)
         if confidence is not None:  # (on the fitted entries, the held-out ones excluded)
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res
@@ -701,6 +828,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         costs_c, costs_s = sol.history()
         res = SolveResult(S=sol.S_pixels(), C=sol.C.clone(), costs_c=costs_c, costs_s=costs_s,
                           nmse=nmse, iters=max_iter, fused=sol.fuse)
+        if polish_s:
+            _polish(res, obs, polish_s, lambda_s, project_s)
         if confidence is not None:
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res
