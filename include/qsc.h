@@ -588,6 +588,89 @@ QSC_API int qsc_sfit(const qsc_obs_desc* d, const void* s_entries, const int32_t
                      int32_t* steps, int32_t* n_unconverged, int32_t* n_unidentified, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-bin projected Newton / Fisher-scoring fit of the spectra for known loss fields (qsc_cfit.hip).
+ *   Conditional on S the likelihood separates over frequency bins.  Bin k minimises over
+ *   c = C[0..R)[k]
+ *     f_k(c) = sum_{positions q observed in bin k} -log max(P(code | t = S[q] . c), FLT_MIN)
+ *              + ridge / 2 |c|^2
+ *   with P, the edges, the log-model chain, the saturation rules and the entry curvature h of
+ *   `kind` exactly as qsc_sinfo / qsc_sfit above (the same device functions).  Per entry
+ *   f += -log max(P, FLT_MIN), g += g_t s_q, J += h s_q s_q^T; a pad entry adds exactly 0;
+ *   P == 0 adds 0 to g and J and -log FLT_MIN to f; in the log model t + offset <= 0 makes
+ *   f = +inf.  The iteration starts at c = C_init[:, k], mu = mu0 and repeats up to max_steps times:
+ *     gamma = g + ridge c;  held set A = {r : c_r <= 0 and gamma_r > 0} with project, else empty
+ *     solve (J + (ridge + mu) I) delta = gamma with the rows and columns of A replaced by the
+ *       identity and gamma_A = 0, so delta_A = 0   (a two-metric projected Newton step)
+ *     c' = c - delta;  project != 0: c' = max(c', 0)
+ *     a pivot (of the free rows) that is not positive: the step counts as rejected
+ *     evaluate (f', g', J') at c'
+ *     accept iff f' <= f and f' is finite: c <- c', mu <- max(mu / 10, mu0 == 0 ? 0 : mu_min)
+ *     else mu <- max(10 mu, mu_min)                                         mu_min = 1e-6
+ *     converged once an accepted step has |c' - c|_inf <= tol (1 + |c|_inf)
+ *   A converged bin stops changing.  With project = 0 this is qsc_sfit's iteration with the roles
+ *   of S and C exchanged.  f is evaluated and summed in fp64 (from the fp32 S, c and edges: the
+ *   accept test compares sums of tens of thousands of terms); g and J are fp32 per partial.
+ *   A bin's entries are spread over all pixel tiles of the C-format lists, so an evaluation is a
+ *   walk (one workgroup per group of tiles, one partial (f, g, triangle of J) per (group, bin),
+ *   the number of groups G fixed by the layout) and a step (one wave per bin: the G partials
+ *   are added in ascending group order in fp64, g and J then rounded to fp32; one lane then
+ *   accepts or rejects against the bin's device-resident state, factors, solves and writes the
+ *   next trial column).  The calls:
+ *     qsc_cfit_begin     state <- C_init, mu0 and the parameters;  walk at C_init
+ *     qsc_cfit_iterate   one step, then the walk at the new trial  (call it up to max_steps times;
+ *                        bins that converged or used max_steps trials no longer change, so
+ *                        further calls are harmless and stopping early once no bin is active
+ *                        gives the same bits)
+ *     qsc_cfit_finish    accepts or rejects the last walked trial and writes the results
+ *   Every call is stream-ordered, never allocates and is capturable into a hipGraph.  There are
+ *   no floating-point atomics: the order of every sum is fixed by the layout, two runs agree
+ *   bit for bit.  S is in position order [Pp][RP] (RP = qsc_rank_pad(R)), C_init / C_out [R][K].
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of the workspace the three calls share (the partials of the G tile groups, at most
+ * 64 MiB: one group per tile while that fits, and the per-bin state: trial and accepted column,
+ * f, g, J, mu, steps, flags); 0 on an invalid descriptor.  Its contents carry the fit from
+ * qsc_cfit_begin to qsc_cfit_finish; one workspace serves one fit at a time. */
+QSC_API size_t qsc_cfit_workspace_bytes(const qsc_obs_desc* d, int32_t R);
+/* G, the number of tile groups (partials per bin) of this layout and rank: min(ntiles, 1024,
+ * 64 MiB / bytes of one group's partials); group g walks tiles [g ntiles / G, (g + 1) ntiles / G).
+ * 0 on an invalid descriptor. */
+QSC_API int32_t qsc_cfit_groups(const qsc_obs_desc* d, int32_t R);
+/* byte offset, in that workspace, of the int32 counter of bins still active (neither converged
+ * nor out of steps) after the last qsc_cfit_iterate: a caller may read it back now and then and
+ * stop iterating at 0 */
+QSC_API int64_t qsc_cfit_active_offset(void);
+/* QSC_EINVAL for m->loss == QSC_LOSS_SQUARED, ridge < 0, mu0 < 0, tol <= 0, max_steps < 1, an
+ * unknown kind, a layout / model mismatch or a workspace smaller than qsc_cfit_workspace_bytes
+ * (qsc_sfit's rules); QSC_EUNSUPPORTED when the S tile (PT rows of RP (+4) floats) and the edges
+ * exceed the 160 KiB of LDS; QSC_EINVAL also for c_entries == NULL (the array always holds its
+ * QSC_ENTRY_TAIL pads).  C_init is copied: it may be the later C_out. */
+QSC_API int qsc_cfit_begin(const qsc_obs_desc* d, const void* c_entries, const int32_t* c_width,
+                           const int64_t* c_off, const int32_t* c_kmap, const qsc_model* m,
+                           int32_t R, const float* S, const float* C_init, int32_t kind,
+                           float ridge, float mu0, float tol, int32_t max_steps, int32_t project,
+                           void* ws, size_t ws_bytes, void* stream);
+/* (the same lists, model, R, S and kind as the qsc_cfit_begin of this workspace) */
+QSC_API int qsc_cfit_iterate(const qsc_obs_desc* d, const void* c_entries, const int32_t* c_width,
+                             const int64_t* c_off, const int32_t* c_kmap, const qsc_model* m,
+                             int32_t R, const float* S, int32_t kind, void* ws, size_t ws_bytes,
+                             void* stream);
+/* C_out[R][K] = the accepted columns;  f_out[K] (nullable, fp64): the final f_k, ridge term
+ * included;  steps[K] (nullable, int32): the trial evaluations the bin used (<= max_steps; the
+ * evaluation at C_init is not counted);  std_C[R][K] (nullable) =
+ * sqrt(diag((J + ridge I)^-1)) of the accepted block (qsc_info_std's Cholesky inverse; the
+ * bound c >= 0 is ignored here: the figure is that of the unconstrained problem, also for
+ * entries held at 0); a non-positive pivot gives +inf for the whole bin, never NaN.
+ * *n_unconverged, *n_unidentified: device int32 counters the caller zeroes, incremented by one
+ * integer atomic per bin concerned:
+ *   n_unconverged   bins that had not converged;
+ *   n_unidentified  bins where, at every step, a pivot p of the free rows of J + (ridge + mu) I
+ *                   had p <= mu (qsc_sfit's rule) -- no observations and ridge = 0, say; such a
+ *                   bin returns C_init unchanged (its g is 0). */
+QSC_API int qsc_cfit_finish(const qsc_obs_desc* d, const qsc_model* m, int32_t R, float* C_out,
+                            double* f_out, int32_t* steps, float* std_C, int32_t* n_unconverged,
+                            int32_t* n_unidentified, void* ws, size_t ws_bytes, void* stream);
+
 /* debug builds (QSC_DEBUG=1, _build.py --debug): the last failed bounds check in the pass
  * kernels (entry offsets, gather-table rows, lane bins; a failed check is recorded and its index
  * clamped, never trapped) as file id * 100000 + source line, 0 if none, -1 in release builds,

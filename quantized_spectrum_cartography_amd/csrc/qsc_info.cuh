@@ -1,11 +1,14 @@
 // qsc_info.cuh — the link terms (P, P', P''), the per-entry curvature and the S-format list walk
-// helpers shared by qsc_info.hip (information blocks) and qsc_sfit.hip (per-pixel Newton fit).
+// helpers shared by qsc_info.hip (information blocks), qsc_sfit.hip (per-pixel Newton fit of S)
+// and qsc_cfit.hip (per-bin Newton fit of C).
 // qsc_info.hip's header has the formulas and the numerics.
 //
 // Everything lives in an anonymous namespace on purpose: each translation unit gets its own
 // (inlined) copy, and the kernels that take a Link by value keep their symbol names.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 #include "qsc_common.cuh"
 
@@ -124,6 +127,62 @@ __host__ __device__ __forceinline__ float entry_curvature(float t, int code,
     }
   }
   return h * tinv2;
+}
+
+// ---- the per-entry terms of the Newton fits (qsc_sfit.hip, qsc_cfit.hip) ----
+// One entry's fp32 f, g_t and h at t (see the file header); `use` is false for what adds 0 to g, J.
+template <bool LOGIT, bool LOG, int KIND>
+__device__ __forceinline__ void entry_terms(float t, int code, const float2* __restrict__ edges,
+                                            const Link& c, float& fe, float& gt, float& h,
+                                            bool& use, bool& neg) {
+  float x = t, ti = 1.0f;
+  neg = false;
+  if (LOG) {
+    const float tp = t + c.offset;
+    neg = !(tp > 0.0f);
+    x = logf(tp);
+    ti = 1.0f / tp;
+  }
+  const float2 e = edges[code];
+  float P, P1, P2;
+  bin_terms<LOGIT>(x, e.x, e.y, c, P, P1, P2);
+  const float ip = 1.0f / P;
+  const float gx = -P1 * ip;
+  fe = -logf(fmaxf(P, FLT_MIN));
+  gt = gx * ti;
+  if (KIND == INFO_OBSERVED) {
+    // entry_curvature<..., INFO_OBSERVED>'s operations on the terms already at hand
+    h = __builtin_fmaf(gx, gx, -P2 * ip);
+    if (LOG) h -= gx;
+    h *= ti * ti;
+  } else {
+    h = entry_curvature<LOGIT, LOG, INFO_EXPECTED>(t, code, edges, c);
+  }
+  use = (P > 0.0f) && !neg;
+}
+
+// F(z) - F(y), z >= y, of the link in fp64, both arguments in the lower half (z + y <= 0) so that
+// neither value is near 1: probit F(z) = erfc(-z) / 2, logit F(z) = e^z / (1 + e^z).
+template <bool LOGIT>
+__device__ __forceinline__ double link_diff(double z, double y) {
+  if (LOGIT) {
+    const double Ez = exp(-fabs(z)), Ey = exp(-fabs(y));
+    const double Fz = z < 0.0 ? Ez / (1.0 + Ez) : 1.0 / (1.0 + Ez);
+    const double Fy = y < 0.0 ? Ey / (1.0 + Ey) : 1.0 / (1.0 + Ey);
+    return Fz - Fy;
+  }
+  return 0.5 * erfc(-z) - 0.5 * erfc(-y);
+}
+
+// One entry's -log max(P, FLT_MIN) in fp64 at t (fp64, from the fp32 s and c_k): bin_terms' P
+// (the same mirroring into the lower half; an infinite edge gives F = 0 or 1 by itself).
+template <bool LOGIT, bool LOG>
+__device__ __forceinline__ double entry_nll(double t, float2 e, const Link& c, double inv_a) {
+  const double x = LOG ? log(t + (double)c.offset) : t;
+  const double u = ((double)e.y - x) * inv_a, w = ((double)e.x - x) * inv_a;
+  const bool mir = (u + w) > 0.0;
+  const double P = link_diff<LOGIT>(mir ? -w : u, mir ? -u : w);
+  return -log(fmax(P, (double)FLT_MIN));
 }
 
 // upper-triangle index of (i, j), i <= j, of an N x N symmetric block

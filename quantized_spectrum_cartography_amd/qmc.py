@@ -40,6 +40,7 @@ class SolveResult:
     std_S: Optional[torch.Tensor] = None  # (R, 1, I, J) standard deviations (solve(confidence=...))
     unidentified: Optional[int] = None  # pixels whose information block is not positive definite
     polish: Optional["FitSResult"] = None  # solve(polish_s=n): the fit_S run on S (without S)
+    polish_c: Optional["FitCResult"] = None  # solve(polish_c=n): the fit_C run on C (without C)
 
 
 @dataclass
@@ -216,6 +217,134 @@ def fit_S(obs, C, S_init=None, ridge=0.0, kind=None, max_steps=30, tol=1e-5, mu0
     return FitSResult(S=obs.to_pixels(S_out, R).reshape(R, 1, obs.I, obs.J), nll=nll,
                       steps=steps[obs.iperm().long()].reshape(obs.I, obs.J),
                       unconverged=unconverged, unidentified=unidentified)
+
+
+@dataclass
+class FitCResult:
+    C: Optional[torch.Tensor]           # (R, K) (None in SolveResult.polish_c)
+    nll: float                          # -sum log P at C over the observed entries (no ridge term)
+    steps: torch.Tensor                 # (K,) int32: trial evaluations each bin used
+    unconverged: int                    # bins not converged within max_steps
+    unidentified: int                   # bins whose J_k + ridge I never had positive pivots
+    std_C: Optional[torch.Tensor] = None  # (R, K) sqrt(diag((J_k + ridge I)^-1)) (std=True)
+
+
+def check_fit_c(loss, ridge, kind, max_steps, tol, mu0):
+    """Validate the fit_C arguments (before anything touches a device)."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: fit_C has nothing to fit')
+    if kind is not None and kind not in INFO_KINDS:
+        raise ValueError("fit_C kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    if not float(ridge) >= 0.0:
+        raise ValueError("the fit_C ridge must be >= 0, got %r" % (ridge,))
+    if not float(mu0) >= 0.0:
+        raise ValueError("mu0 must be >= 0, got %r" % (mu0,))
+    if not float(tol) > 0.0:
+        raise ValueError("tol must be > 0, got %r" % (tol,))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1, got %r" % (max_steps,))
+
+
+def _fit_c_pos(obs, S_pos, C_init, R, kind, ridge, max_steps, tol, mu0, project, std=False,
+               sync_every=4, C_out=None, ws=None):
+    """qsc_cfit_begin / _iterate / _finish on a position-order S (Pp, RP) and a device C_init
+    (R, K): (C_out, f (K,) fp64, steps (K,) int32, counters (2,) int32: unconverged,
+    unidentified, std_C or None), all on the device.  With sync_every = 0 nothing is read back
+    (the sequence can be captured into a hipGraph)."""
+    desc, _, c_entries = obs.layout(R)
+    dev = S_pos.device
+    K = obs.K
+    if C_out is None:
+        C_out = torch.empty((R, K), dtype=torch.float32, device=dev)
+    f = torch.empty(K, dtype=torch.float64, device=dev)
+    steps = torch.empty(K, dtype=torch.int32, device=dev)
+    std_C = torch.empty((R, K), dtype=torch.float32, device=dev) if std else None
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_cfit_workspace_bytes(desc, R))
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    lists = (desc, _lib.ptr(c_entries), _lib.ptr(obs.c_width), _lib.ptr(obs.c_off),
+             _lib.ptr(obs.c_kmap), obs.model, R, _lib.ptr(S_pos))
+    _lib.call("qsc_cfit_begin", *lists, _lib.ptr(C_init), INFO_KINDS[kind], float(ridge),
+              float(mu0), float(tol), int(max_steps), 1 if project else 0, _lib.ptr(ws), nws,
+              _lib.stream())
+    o = int(_lib.lib().qsc_cfit_active_offset())
+    active = ws[o:o + 4].view(torch.int32)
+    for i in range(1, int(max_steps) + 1):
+        _lib.call("qsc_cfit_iterate", *lists, INFO_KINDS[kind], _lib.ptr(ws), nws, _lib.stream())
+        if sync_every and i % int(sync_every) == 0 and int(active.item()) == 0:
+            break
+    _lib.call("qsc_cfit_finish", desc, obs.model, R, _lib.ptr(C_out), _lib.ptr(f), _lib.ptr(steps),
+              _lib.ptr(std_C), _lib.ptr(counters[0:1]), _lib.ptr(counters[1:2]), _lib.ptr(ws), nws,
+              _lib.stream())
+    return C_out, f, steps, counters, std_C
+
+
+def fit_C(obs, S, C_init=None, ridge=0.0, kind=None, max_steps=30, tol=1e-5, mu0=1e-3,
+          project=True, std=False, sync_every=4):
+    """The spectra C for known loss fields S: per frequency bin, a projected damped Newton /
+    Fisher-scoring fit of the quantized likelihood -- the mirror image of fit_S.
+
+    Given S the likelihood separates over bins; bin k minimises over c = C[:, k]
+      f_k(c) = sum_{p observed in bin k} -log P(Y[k, p] | S[:, p] . c) + ridge / 2 |c|^2,
+    R unknowns informed by every observed pixel of the bin.  A HIP walk over the packed
+    C-format lists (qsc_cfit.hip, include/qsc.h has the iteration) evaluates f, its gradient and
+    the R x R curvature block of every bin at a trial C; a second kernel accepts the trial when
+    f does not increase (else raises the damping mu), solves (J + (ridge + mu) I) delta =
+    g + ridge c on the entries that are not held at the bound, and proposes the next trial, until
+    |delta|_inf <= tol (1 + |c|_inf) or max_steps.  project=True (default: C >= 0 is the
+    solver's standing constraint) makes it a two-metric projected Newton method: entries at 0
+    whose gradient points outwards are held, the rest take the Newton step and are clipped.
+    obs: the Observations; S (R,1,I,J) or (R,P) from a propagation model, a survey or an earlier
+    solve.  C_init (R,K): default zeros (linear model) or ones (log model).  kind "observed"
+    (default for the linear model) or "expected" (default for the log model).  std=True also
+    returns std_C = sqrt(diag((J_k + ridge I)^-1)) at the result (the bound ignored; +inf for a
+    bin whose block is not positive definite).  sync_every: every so many steps the count of
+    active bins is read back and the loop stops at 0 (0: never; the result is the same bits).
+    Returns FitCResult(C (R,K), nll, steps (K,), unconverged, unidentified, std_C or None): nll is
+    the NLL at C without the ridge term (fp64 sums in a fixed order); unidentified counts bins
+    whose J_k + ridge I never had all pivots positive (no observations and ridge = 0: such a bin
+    keeps C_init).  Raises ValueError for loss="squared", negative ridge / mu0, tol <= 0,
+    max_steps < 1 or an unknown kind, before any GPU call."""
+    check_fit_c(getattr(obs, "loss", None), ridge, kind, max_steps, tol, mu0)
+    log_model = bool(getattr(obs, "log_model", False))
+    if kind is None:
+        kind = "expected" if log_model else "observed"
+    R = S.shape[0]
+    if C_init is None:
+        C_init = (torch.ones if log_model else torch.zeros)(R, obs.K)
+    S_pos = obs.to_positions(S.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C_init.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    C_out, f, steps, counters, std_C = _fit_c_pos(obs, S_pos, Cd, R, kind, ridge, max_steps, tol,
+                                                  mu0, project, std=std, sync_every=sync_every)
+    nll = float(f.sum() - 0.5 * float(ridge) * (C_out.double() ** 2).sum())
+    unconverged, unidentified = counters.tolist()
+    return FitCResult(C=C_out, nll=nll, steps=steps, unconverged=unconverged,
+                      unidentified=unidentified, std_C=std_C)
+
+
+def check_polish_c(polish_c, generator, loss):
+    """Validate solve(polish_c=...) (before anything touches a device); the step count.  The
+    smoothness prior is allowed: it does not involve C."""
+    n = int(polish_c)
+    if n < 0:
+        raise ValueError("polish_c must be >= 0, got %r" % (polish_c,))
+    if n > 0:
+        if generator is not None:
+            raise ValueError("polish_c applies to free S only: with a generator the solve does "
+                             "not return a free S to condition on")
+        if loss == "squared":
+            raise ValueError('polish_c needs a likelihood: loss="squared" has none')
+    return n
+
+
+def _polish_c(res, obs, n, lambda_c):
+    """solve(polish_c=n): C <- fit_C from the returned C at the returned S."""
+    r = fit_C(obs, res.S, C_init=res.C, ridge=default_confidence_ridge(res.C, lambda_c),
+              max_steps=n, project=True)
+    res.C, r.C = r.C, None
+    res.polish_c = r
+    return res
 
 
 def check_polish(polish_s, generator, loss, smooth):
@@ -698,7 +827,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
-          confidence_ridge=None, polish_s=0):
+          confidence_ridge=None, polish_s=0, polish_c=0):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -753,6 +882,12 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     about; result.polish is the FitSResult (without S).  Raises ValueError with a generator, with
     loss="squared" and with smooth > 0: the fit treats every pixel on its own, and the
     smoothness prior couples pixels.  The default 0 leaves every path and result bit-identical.
+    polish_c=n > 0 (free S and holdout solves; not in the reference): after the loop and the
+    holdout restore, and before polish_s, C is replaced by qmc.fit_C started from it at the
+    returned S, for up to n projected Newton steps per bin with the ridge lambda_c / ||C||_F --
+    so a following polish_s fits S at the polished C.  result.polish_c is the FitCResult (without
+    C).  Raises ValueError with a generator and with loss="squared"; smooth > 0 is allowed (the
+    prior does not involve C).  The default 0 leaves every path and result bit-identical.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
     smooth = check_smooth(smooth, smooth_kind, smooth_delta)
@@ -760,6 +895,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         raise ValueError("smooth > 0 applies to free S only: a generator already carries the "
                          "spatial prior")
     polish_s = check_polish(polish_s, generator, obs.loss if obs is not None else loss, smooth)
+    polish_c = check_polish_c(polish_c, generator, obs.loss if obs is not None else loss)
     if confidence is not None:
         check_confidence(confidence, confidence_ridge, obs.loss if obs is not None else loss)
         if generator is not None:
@@ -796,6 +932,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         res = _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s,
                              max_iter, betas, eps, project_c, fuse, project_s, use_graph,
                              int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
+        if polish_c:
+            _polish_c(res, obs, polish_c, lambda_c)
         if polish_s:
             _polish(res, obs, polish_s, lambda_s, project_s)
         if confidence is not None:  # (on the fitted entries, the held-out ones excluded)
@@ -828,6 +966,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         costs_c, costs_s = sol.history()
         res = SolveResult(S=sol.S_pixels(), C=sol.C.clone(), costs_c=costs_c, costs_s=costs_s,
                           nmse=nmse, iters=max_iter, fused=sol.fuse)
+        if polish_c:
+            _polish_c(res, obs, polish_c, lambda_c)
         if polish_s:
             _polish(res, obs, polish_s, lambda_s, project_s)
         if confidence is not None:
