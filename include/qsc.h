@@ -589,6 +589,79 @@ QSC_API int qsc_sfit(const qsc_obs_desc* d, const void* s_entries, const int32_t
                      size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Newton fit of the loss fields under the smoothness prior: red-black visits (qsc_sfit_smooth.hip).
+ *   The prior weight * R(S) (qsc_smooth_grad above) couples each pixel to its 4 grid neighbours.
+ *   That graph is bipartite in the colour (i + j) & 1 of pixel p = i*J + j: with the rows of the
+ *   other colour held fixed, the own-colour positions are independent again.  Position q of
+ *   colour c minimises over s = S[q][0..R)
+ *     phi_q(s) = f_q(s) + weight * sum_{n in N(q)} sum_{r<R} rho(s_r - S[n][r])
+ *   with f_q qsc_sfit's objective (ridge included), N(q) the 2..4 existing entries of nbr[q] (all
+ *   of colour 1 - c) and rho of QSC_SMOOTH_QUAD / _HUBER.  Every edge joins the two colours, so
+ *     sum_{q of colour c} phi_q + sum_{q of colour 1 - c} f_q
+ *       = F(S) = NLL + ridge / 2 |S|^2 + weight * R(S),   each edge once:
+ *   a visit in which every position accepts a step only when its own phi_q does not increase
+ *   leaves F non-increasing, and alternating the colours is block coordinate descent on F
+ *   (convex under the linear model).
+ *   One launch is one visit of one colour, in place on S[Pp][RP] (position order).  Position q
+ *   takes part iff p = perm[q] >= 0 and ((p / J) + (p % J)) & 1 == color; positions of the other
+ *   colour and padding positions are neither changed nor written.  The neighbour rows a visit
+ *   reads are of the other colour, so no row read as a neighbour is written in the same launch:
+ *   no race, no second buffer, no dependence on grid or wave order.
+ *   Per own-colour position: qsc_sfit's walk gives (f, g, J) of f_q at the trial point; then each
+ *   existing neighbour n (in the order left, right, up, down) and each r < R adds, with
+ *   d = s_r - S[n][r]:
+ *     f    += weight * rho(d)     in fp64 from the fp32 operands
+ *     g_r  += weight * rho'(d)    QUAD: d;   HUBER: clamp(d / delta, -1, 1)
+ *     J_rr += weight * kappa(d)   QUAD: 1;   HUBER: 1 / max(|d|, delta), the half-quadratic
+ *                                 majoriser (rho'' for |d| <= delta, positive outside, so that a
+ *                                 step is defined where rho'' = 0)
+ *   and qsc_sfit's iteration runs on (phi, g, J) unchanged:
+ *     evaluate at s = S[q];  mu = mu0   (mu restarts every visit; no per-position state is kept
+ *                                        between launches)
+ *     repeat up to inner_steps times:
+ *       solve (J + (ridge + mu) I) delta = g + ridge s;  s' = s - delta;  project: s' = max(s', 0)
+ *       a pivot that is not positive: the step counts as rejected
+ *       evaluate (phi', g', J') at s'
+ *       accept iff phi' <= phi and phi' is finite: s <- s', mu <- max(mu / 10, mu0 == 0 ? 0 : mu_min)
+ *       else mu <- max(10 mu, mu_min)                                       mu_min = 1e-6
+ *       converged once an accepted step has |s' - s|_inf <= tol (1 + |s|_inf)
+ *   The neighbour rows are re-read (16-byte vectors, from the cache) after every walk; nothing of
+ *   them is staged in LDS or registers.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of workspace qsc_sfit_smooth needs: qsc_sfit_workspace_bytes' rule (0 for R <= 8; for
+ * R > 8 one row of the accepted (g, J) per lane of the grid, reused across slices). */
+QSC_API size_t qsc_sfit_smooth_workspace_bytes(const qsc_obs_desc* d, int32_t R);
+/* One visit of colour `color` (0 or 1), in place on S.  nbr[Pp][4]: qsc_smooth_neighbors' table
+ * of the same perm (-1: no neighbour; an entry outside [0, Pp) is read as none); I * J == d->P.
+ * Lists, perm, m, R, C, kind, ridge, mu0, tol, project as qsc_sfit; smooth_kind, delta, weight as
+ * qsc_smooth_grad (delta is read for QSC_SMOOTH_HUBER only; weight = 0 makes a visit qsc_sfit's
+ * iteration on the colour's positions).  Outputs, written for own-colour positions only:
+ *   f_out[Pp]   (nullable) the final phi_q;
+ *   nll_out[Pp] (nullable) its likelihood part alone, without the ridge and the prior: it depends
+ *               on the position's own row only, so it stays valid after visits of the other colour;
+ *   steps[Pp]   (nullable, int32) += the trial evaluations of this visit (the caller zeroes it);
+ * and device int32 counters the caller zeroes, each incremented by one integer atomic per wave:
+ *   n_moved        own-colour positions whose row changed over the visit by more than
+ *                  tol (1 + |s_start|_inf) in the infinity norm;
+ *   n_unconverged  those that had not converged after inner_steps;
+ *   n_unidentified qsc_sfit's pivot rule on the matrix with the prior's diagonal: a position
+ *                  without observations at ridge 0 is identified through its neighbours.
+ * No floating-point atomics; two calls from the same S agree bit for bit.  Stream-ordered, never
+ * allocates, capturable into a hipGraph.  QSC_EINVAL for everything qsc_sfit rejects and for
+ * color outside {0, 1}, weight < 0, an unknown smooth_kind, HUBER with delta <= 0,
+ * inner_steps < 1, I * J != d->P or a workspace smaller than qsc_sfit_smooth_workspace_bytes;
+ * QSC_EUNSUPPORTED by qsc_sfit's LDS rule (the neighbour rows take no LDS) and beyond
+ * qsc_smooth_grad's 2^28 positions. */
+QSC_API int qsc_sfit_smooth(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                            const int64_t* s_off, const int32_t* perm, const int32_t* nbr,
+                            int32_t I, int32_t J, int32_t color, const qsc_model* m, int32_t R,
+                            const float* C, float* S, int32_t kind, float ridge, float mu0,
+                            float tol, int32_t inner_steps, int32_t project, int32_t smooth_kind,
+                            float delta, float weight, float* f_out, float* nll_out,
+                            int32_t* steps, int32_t* n_moved, int32_t* n_unconverged,
+                            int32_t* n_unidentified, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Per-bin projected Newton / Fisher-scoring fit of the spectra for known loss fields (qsc_cfit.hip).
  *   Conditional on S the likelihood separates over frequency bins.  Bin k minimises over
  *   c = C[0..R)[k]

@@ -41,6 +41,8 @@ class SolveResult:
     unidentified: Optional[int] = None  # pixels whose information block is not positive definite
     polish: Optional["FitSResult"] = None  # solve(polish_s=n): the fit_S run on S (without S)
     polish_c: Optional["FitCResult"] = None  # solve(polish_c=n): the fit_C run on C (without C)
+    # solve(polish_smooth=n): the fit_S_smooth run on S (without S)
+    polish_smooth: Optional["FitSSmoothResult"] = None
 
 
 @dataclass
@@ -370,6 +372,180 @@ def _polish(res, obs, n, lambda_s, project_s):
               max_steps=n, project=project_s)
     res.S, r.S = r.S, None
     res.polish = r
+    return res
+
+
+@dataclass
+class FitSSmoothResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J), pixel order (None in SolveResult.polish_smooth)
+    nll: float                          # -sum log P at S over the observed entries
+    penalty: float                      # R(S), unweighted (qsc_smooth_grad)
+    objective: float                    # nll + ridge / 2 |S|^2 + smooth * penalty
+    sweeps: int                         # sweeps run (a sweep: colour 0, then colour 1)
+    steps: torch.Tensor                 # (I, J) int32: trial evaluations each pixel used in all
+    moved: int                          # pixels the last sweep moved by more than tol (1 + |s|_inf)
+    unconverged: int                    # pixels of the last sweep whose last trial was not an
+                                        # accepted step within tol (stalled pixels among them)
+    unidentified: int                   # pixels of the last sweep whose J + prior + ridge never
+                                        # had positive pivots
+
+
+def check_fit_s_smooth(loss, smooth, smooth_kind, smooth_delta, ridge, kind, sweeps, inner_steps,
+                       tol, mu0):
+    """Validate the fit_S_smooth arguments (before anything touches a device); float(smooth)."""
+    if int(inner_steps) < 1:
+        raise ValueError("inner_steps must be >= 1, got %r" % (inner_steps,))
+    check_fit_s(loss, ridge, kind, inner_steps, tol, mu0)
+    smooth = check_smooth(smooth, smooth_kind, smooth_delta)
+    if not smooth > 0.0:
+        raise ValueError("fit_S_smooth needs smooth > 0, got %r: without the prior the pixels are "
+                         "independent and fit_S fits them in one launch" % (smooth,))
+    if int(sweeps) < 1:
+        raise ValueError("sweeps must be >= 1, got %r" % (sweeps,))
+    return smooth
+
+
+def _sfit_smooth_bufs(obs, R, sweeps):
+    """The device buffers of a run of visits: (f, nll, steps (zeroed), counters (sweeps, 2, 3)
+    int32 zeroed -- one (n_moved, n_unconverged, n_unidentified) triple per visit, so that no
+    launch waits for a reset -- and the workspace or None)."""
+    desc, _, _ = obs.layout(R)
+    dev = obs.device
+    f = torch.zeros(obs.Pp, dtype=torch.float32, device=dev)
+    nll = torch.zeros(obs.Pp, dtype=torch.float32, device=dev)
+    steps = torch.zeros(obs.Pp, dtype=torch.int32, device=dev)
+    counters = torch.zeros((int(sweeps), 2, 3), dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_sfit_smooth_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    return f, nll, steps, counters, ws
+
+
+def _sfit_smooth_visit(obs, S_pos, C, R, color, kind, ridge, inner_steps, tol, mu0, project,
+                       smooth_code, delta, weight, f, nll, steps, cnt, ws):
+    """qsc_sfit_smooth: one visit of one colour, in place on the position-order S_pos (Pp, RP);
+    cnt a (3,) int32 device view (n_moved, n_unconverged, n_unidentified) the call adds to."""
+    desc, s_entries, _ = obs.layout(R)
+    _lib.call("qsc_sfit_smooth", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width),
+              _lib.ptr(obs.s_off), _lib.ptr(obs.perm), _lib.ptr(obs.neighbors()), obs.I, obs.J,
+              int(color), obs.model, R, _lib.ptr(C), _lib.ptr(S_pos), INFO_KINDS[kind],
+              float(ridge), float(mu0), float(tol), int(inner_steps), 1 if project else 0,
+              smooth_code, float(delta), float(weight), _lib.ptr(f), _lib.ptr(nll),
+              _lib.ptr(steps), _lib.ptr(cnt[0:1]), _lib.ptr(cnt[1:2]), _lib.ptr(cnt[2:3]),
+              _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream())
+
+
+def _fit_s_smooth_pos(obs, S_pos, C, R, kind, ridge, sweeps, inner_steps, tol, mu0, project,
+                      smooth_kind_, smooth_delta, weight, sync_every=4):
+    """Red-black sweeps of qsc_sfit_smooth in place on S_pos: (nll (Pp,), steps (Pp,),
+    counters (sweeps, 2, 3), sweeps run).  With sync_every = 0 nothing is read back."""
+    from .fused import smooth_kind as _kind_code
+    code, delta = _kind_code(smooth_kind_, smooth_delta)
+    f, nll, steps, counters, ws = _sfit_smooth_bufs(obs, R, sweeps)
+    n = 0
+    for i in range(int(sweeps)):
+        for color in (0, 1):
+            _sfit_smooth_visit(obs, S_pos, C, R, color, kind, ridge, inner_steps, tol, mu0,
+                               project, code, delta, weight, f, nll, steps, counters[i, color], ws)
+        n = i + 1
+        if sync_every and n % int(sync_every) == 0 and int(counters[i, :, 0].sum().item()) == 0:
+            break
+    return nll, steps, counters, n
+
+
+def _smooth_penalty_pos(obs, S_pos, R, smooth_kind_, smooth_delta):
+    """R(S), unweighted, of a position-order S (qsc_smooth_grad with dS = NULL); synchronises."""
+    from .fused import smooth_kind as _kind_code
+    code, delta = _kind_code(smooth_kind_, smooth_delta)
+    dev = S_pos.device
+    nb = int(_lib.lib().qsc_smooth_workspace_bytes(obs.Pp))
+    if nb == 0:
+        raise _lib.QscError("the smoothness prior does not support Pp = %d" % obs.Pp)
+    ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    pen = torch.zeros(1, dtype=torch.float32, device=dev)
+    _lib.call("qsc_smooth_grad", _lib.ptr(S_pos), _lib.ptr(obs.neighbors()), R, obs.Pp, code,
+              delta, 1.0, None, _lib.ptr(pen), None, 0, _lib.ptr(ws), ws.numel(), _lib.stream())
+    return float(pen.item())
+
+
+def fit_S_smooth(obs, C, smooth, smooth_kind="quad", smooth_delta=None, S_init=None, ridge=0.0,
+                 kind=None, sweeps=20, inner_steps=2, tol=1e-5, mu0=1e-3, project=None,
+                 sync_every=4):
+    """The loss fields S for known spectra C under the smoothness prior: red-black Newton sweeps.
+
+    Minimises F(S) = NLL(S) + ridge / 2 |S|^2 + smooth * R(S), R the prior of solve(smooth=...)
+    ("quad" or "huber" with smooth_delta).  The prior couples each pixel to its 4 grid neighbours
+    only, and that graph is bipartite in the colour (i + j) & 1: with one colour held fixed the
+    pixels of the other are independent, and each takes up to inner_steps damped Newton steps of
+    fit_S's iteration on its own phi = f + smooth * (prior terms of its edges) in one HIP launch
+    (qsc_sfit_smooth, include/qsc.h).  A sweep is colour 0 then colour 1; every accepted step
+    lowers its pixel's phi, so F never increases (block coordinate descent; F is convex under the
+    linear model).  A pixel without observations is determined by its neighbours.
+    obs, C, S_init, ridge, kind, tol, mu0, project: as fit_S (the same defaults).  Every
+    sync_every sweeps the count of pixels the sweep moved by more than tol (1 + |s|_inf) is read
+    back and the fit stops at 0 (sync_every=0: never, all sweeps run; the result is the same bits
+    where none stops early).  A visit restarts the damping at mu0 and has inner_steps trials: a
+    pixel whose trials are all rejected (far in a link's tail, from S = 0 under the logit or log
+    model, say) does not move and is not counted in `moved`, so start such fits from a solver's
+    S, as polish_smooth does, or raise inner_steps.  `unconverged` counts the pixels whose last
+    trial of the last sweep was not an accepted step within tol: every stalled pixel, but also
+    the many pixels of a converged fit whose last, rounding-sized step is rejected (117 of 135
+    against a stall's 134 on the logit test input), so it is a hint, not a test of convergence.
+    Returns FitSSmoothResult(S (R,1,I,J), nll, penalty, objective, sweeps, steps (I,J), moved,
+    unconverged, unidentified): nll the fp64 sum of the per-pixel NLL in a fixed order, penalty R(S) unweighted
+    (qsc_smooth_grad), objective = nll + ridge / 2 |S|^2 + smooth * penalty, moved and
+    unidentified of the last sweep run.  Raises ValueError for smooth <= 0 (use fit_S), sweeps or
+    inner_steps < 1, an unknown smooth_kind, huber without delta > 0 and everything fit_S raises
+    for, before any GPU call."""
+    smooth = check_fit_s_smooth(getattr(obs, "loss", None), smooth, smooth_kind, smooth_delta,
+                                ridge, kind, sweeps, inner_steps, tol, mu0)
+    log_model = bool(getattr(obs, "log_model", False))
+    if kind is None:
+        kind = "expected" if log_model else "observed"
+    if project is None:
+        project = log_model
+    R = C.shape[0]
+    if S_init is None:
+        S_init = (torch.ones if log_model else torch.zeros)(R, obs.P)
+    S_pos = obs.to_positions(S_init.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    nll_pos, steps, counters, n = _fit_s_smooth_pos(obs, S_pos, Cd, R, kind, ridge, sweeps,
+                                                    inner_steps, tol, mu0, project, smooth_kind,
+                                                    smooth_delta, smooth, sync_every=sync_every)
+    pen = _smooth_penalty_pos(obs, S_pos, R, smooth_kind, smooth_delta)
+    nll = float(nll_pos.double().sum())
+    normsq = float((S_pos.double() ** 2).sum())
+    moved, unconverged, unidentified = counters[n - 1].sum(dim=0).tolist()
+    return FitSSmoothResult(S=obs.to_pixels(S_pos, R).reshape(R, 1, obs.I, obs.J), nll=nll,
+                            penalty=pen, objective=nll + 0.5 * float(ridge) * normsq + smooth * pen,
+                            sweeps=n, steps=steps[obs.iperm().long()].reshape(obs.I, obs.J),
+                            moved=int(moved), unconverged=int(unconverged),
+                            unidentified=int(unidentified))
+
+
+def check_polish_smooth(polish_smooth, generator, loss, smooth):
+    """Validate solve(polish_smooth=...) (before anything touches a device); the sweep count."""
+    n = int(polish_smooth)
+    if n < 0:
+        raise ValueError("polish_smooth must be >= 0, got %r" % (polish_smooth,))
+    if n > 0:
+        if generator is not None:
+            raise ValueError("polish_smooth applies to free S only: with a generator S is not a "
+                             "free parameter")
+        if loss == "squared":
+            raise ValueError('polish_smooth needs a likelihood: loss="squared" has none')
+        if not smooth > 0.0:
+            raise ValueError("polish_smooth fits S under the smoothness prior: it needs "
+                             "smooth > 0 (without the prior, polish_s fits every pixel on its own)")
+    return n
+
+
+def _polish_smooth(res, obs, n, lambda_s, project_s, smooth, smooth_kind, smooth_delta):
+    """solve(polish_smooth=n): S <- n sweeps of fit_S_smooth from the returned S at the returned C."""
+    r = fit_S_smooth(obs, res.C, smooth, smooth_kind=smooth_kind, smooth_delta=smooth_delta,
+                     S_init=res.S, ridge=default_confidence_ridge(res.S, lambda_s), sweeps=n,
+                     project=project_s)
+    res.S, r.S = r.S, None
+    res.polish_smooth = r
     return res
 
 
@@ -827,7 +1003,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
-          confidence_ridge=None, polish_s=0, polish_c=0):
+          confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -888,6 +1064,13 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     so a following polish_s fits S at the polished C.  result.polish_c is the FitCResult (without
     C).  Raises ValueError with a generator and with loss="squared"; smooth > 0 is allowed (the
     prior does not involve C).  The default 0 leaves every path and result bit-identical.
+    polish_smooth=n > 0 (free S and holdout solves with smooth > 0; not in the reference): after
+    polish_c and before confidence=, S is replaced by n red-black sweeps of qmc.fit_S_smooth
+    started from it at the returned C, under the solve's own smooth, smooth_kind and smooth_delta
+    and the ridge lambda_s / ||S||_F of polish_s: the second-order fit for the solves polish_s
+    refuses.  result.polish_smooth is the FitSSmoothResult (without S).  Raises ValueError with
+    smooth = 0, with a generator and with loss="squared".  The default 0 leaves every path and
+    result bit-identical.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
     smooth = check_smooth(smooth, smooth_kind, smooth_delta)
@@ -896,6 +1079,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
                          "spatial prior")
     polish_s = check_polish(polish_s, generator, obs.loss if obs is not None else loss, smooth)
     polish_c = check_polish_c(polish_c, generator, obs.loss if obs is not None else loss)
+    polish_smooth = check_polish_smooth(polish_smooth, generator,
+                                        obs.loss if obs is not None else loss, smooth)
     if confidence is not None:
         check_confidence(confidence, confidence_ridge, obs.loss if obs is not None else loss)
         if generator is not None:
@@ -936,6 +1121,9 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
             _polish_c(res, obs, polish_c, lambda_c)
         if polish_s:
             _polish(res, obs, polish_s, lambda_s, project_s)
+        if polish_smooth:
+            _polish_smooth(res, obs, polish_smooth, lambda_s, project_s, smooth, smooth_kind,
+                           smooth_delta)
         if confidence is not None:  # (on the fitted entries, the held-out ones excluded)
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res
@@ -970,6 +1158,9 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
             _polish_c(res, obs, polish_c, lambda_c)
         if polish_s:
             _polish(res, obs, polish_s, lambda_s, project_s)
+        if polish_smooth:
+            _polish_smooth(res, obs, polish_smooth, lambda_s, project_s, smooth, smooth_kind,
+                           smooth_delta)
         if confidence is not None:
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res
