@@ -3,16 +3,11 @@
 // qsc_cfit_finish).
 //
 // Conditional on S the likelihood separates over frequency bins; bin k minimises, over
-// c = C[0..R)[k],
-//     f_k(c) = sum_{positions q observed in bin k} -log max(P(code | t = S[q] . c), FLT_MIN)
-//              + ridge / 2 |c|^2
-// with P, the edges, the log-model chain and the saturation rules of qsc_info.cuh, and per entry
-// (entry_terms / entry_nll of qsc_info.cuh, the functions qsc_sfit.hip evaluates)
-//     f += -log max(P, FLT_MIN)   (fp64),   g += g_t s_q,   J += h s_q s_q^T   (fp32)
-// A pad entry adds exactly 0; P == 0 adds 0 to g and J and -log FLT_MIN to f; in the log model
-// t + offset <= 0 makes f = +inf.  This is qsc_sfit's problem with the roles of S and C exchanged,
-// but a bin's entries are spread over every pixel tile of the C-format lists, so the evaluation
-// and the R x R solve are two kernels with a fixed-order reduction between them.
+// c = C[0..R)[k], qsc_newton.cuh's objective with the table rows s_q = S[q] of the positions
+// observed in the bin: qsc_sfit's problem with the roles of S and C exchanged, with the same
+// per-entry terms, accept rule, mu schedule and factorisation (that header).  But a bin's entries
+// are spread over every pixel tile of the C-format lists, so the evaluation and the R x R solve
+// are two kernels with a fixed-order reduction between them.
 //
 // cfit_eval_kernel: the walk.  The work unit is the C-pass's: (pixel tile, 64-bin k-slice),
 // lane = bin c_kmap[(t nks + ks) 64 + lane].  One workgroup owns a fixed, contiguous group of
@@ -42,18 +37,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 
 #include "qsc_common.cuh"
-#include "qsc_info.cuh"
+#include "qsc_newton.cuh"
 
 namespace {
 using namespace qsc;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 constexpr int kStepBlock = 64;
-constexpr float kMuMin = 1.0e-6f;  // qsc_sfit's: the smallest non-zero damping
 // the most partial bytes one call may ask for; beyond it tiles share a group
 constexpr size_t kPartialCap = (size_t)64 << 20;
 constexpr int kMaxGroups = 1024;
@@ -79,7 +70,6 @@ struct CfitWs {
   int* flags;   // [K]
 };
 
-__host__ __device__ constexpr int tri_count(int RP) { return RP * (RP + 1) / 2; }
 // floats of one (g, J) row: g[RP], the triangle of J, padded to whole 16-byte vectors
 __host__ __device__ constexpr int row_floats(int RP) { return (RP + tri_count(RP) + 3) & ~3; }
 
@@ -206,40 +196,9 @@ __global__ void __launch_bounds__(kBlock) cfit_eval_kernel(
           bool pad;
           decode<E, SR>(v[e], PT, Qo, lk.nbins, q, code, pad);
           float sv[RP];
-#pragma unroll
-          for (int r = 0; r < RP; r += 4) {
-            const float4 x = *reinterpret_cast<const float4*>(Sl + (size_t)q * SP + r);
-            sv[r] = x.x;
-            sv[r + 1] = x.y;
-            sv[r + 2] = x.z;
-            sv[r + 3] = x.w;
-          }
-          float tt = 0.0f;
-#pragma unroll
-          for (int r = 0; r < RP; ++r) tt = __builtin_fmaf(cv[r], sv[r], tt);
-          double td = 0.0;
-#pragma unroll
-          for (int r = 0; r < RP; ++r) td = __builtin_fma((double)cv[r], (double)sv[r], td);
-          float fe, ge, hh;
-          bool use, eneg;
-          entry_terms<LOGIT, LOG, KIND>(tt, code, El, lk, fe, ge, hh, use, eneg);
-          // the fp32 P == 0 (FLT_MIN's term) and t + offset <= 0 (f = +inf below) keep their rule
-          const double fd = (fe == -logf(FLT_MIN) || eneg)
-                                ? (double)fe
-                                : entry_nll<LOGIT, LOG>(td, El[code], lk, inv_a);
-          use = use && !pad;  // a pad adds exactly 0 (s_q is finite)
-          ft += pad ? 0.0 : fd;
-          neg = neg || (eneg && !pad);
-          ge = use ? ge : 0.0f;
-          hh = use ? hh : 0.0f;
-#pragma unroll
-          for (int i = 0; i < RP; ++i) {
-            gt[i] = __builtin_fmaf(ge, sv[i], gt[i]);
-            const float hi_ = hh * sv[i];
-#pragma unroll
-            for (int j = i; j < RP; ++j)
-              Jt[tri<RP>(i, j)] = __builtin_fmaf(hi_, sv[j], Jt[tri<RP>(i, j)]);
-          }
+          QSC_ROW_LOAD(RP, sv, Sl + (size_t)q * SP)
+          QSC_ENTRY_ACCUMULATE(RP, LOGIT, LOG, KIND, cv, sv, code, pad, El, lk, inv_a, ft, neg, gt,
+                               Jt)
         }
       }
       ft = neg ? (double)__builtin_inff() : ft;
@@ -314,7 +273,7 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
   constexpr int NA = row_floats(RP);
   const int k = blockIdx.x, lane = threadIdx.x;
   const CfitParams pr = *w.prm;
-  const float mu_floor = pr.mu0 == 0.0f ? 0.0f : kMuMin;
+  const float mu_floor = QSC_MU_FLOOR(pr.mu0);
   int fl = w.flags[k];
   int nwalk = w.nwalk[k];
   const bool first = (fl & FLAG_FIRST) != 0;
@@ -337,14 +296,7 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
     ft += 0.5 * (double)pr.ridge * nsq;
     const double fc = w.fc[k];
     const bool step_ok = (fl & FLAG_STEP_OK) != 0;
-    const bool acc = first || (step_ok && ft <= fc && fabs(ft) < (double)__builtin_inff());
-    float dmax = 0.0f, smax = 0.0f;
-#pragma unroll
-    for (int r = 0; r < RP; ++r) {
-      dmax = fmaxf(dmax, fabsf(ct[r] - ca[r]));
-      smax = fmaxf(smax, fabsf(ca[r]));
-    }
-    const bool conv = !first && acc && dmax <= pr.tol * (1.0f + smax);
+    QSC_NEWTON_ACCEPT(RP, first, step_ok, ft, fc, ct, ca, pr.tol);
     nwalk += first ? 0 : 1;
     if (acc) {
       // the accepted gradient and block: fp64 sums in group order, rounded to fp32 once
@@ -358,9 +310,9 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
         for (int r = 0; r < RP; ++r)
           if (r < R) w.Ca[(int64_t)r * K + k] = ct[r];
       }
-      if (!first) mu = fmaxf(mu / 10.0f, mu_floor);
+      QSC_MU_ACCEPTED(mu, first, mu_floor);
     } else {
-      mu = fmaxf(10.0f * mu, kMuMin);
+      QSC_MU_REJECTED(mu);
     }
     done = conv;
     fl &= ~(FLAG_FIRST | FLAG_DONE);
@@ -395,45 +347,7 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
         a[tri<RP>(i, j)] = v;
       }
     }
-    float dinv[RP], y[RP];
-    bool ok = true, idn = true;
-#pragma unroll
-    for (int j = 0; j < RP; ++j) {
-      float piv = a[tri<RP>(j, j)];
-#pragma unroll
-      for (int i = 0; i < j; ++i) piv = __builtin_fmaf(-a[tri<RP>(i, j)], a[tri<RP>(i, j)], piv);
-      if (!held[j]) {
-        idn = idn && (piv > mu);
-        if (!(piv > 0.0f)) {  // (also a NaN block)
-          ok = false;
-          piv = 1.0f;
-        }
-      }
-      const float d = sqrtf(piv);
-      dinv[j] = 1.0f / d;
-#pragma unroll
-      for (int i = j + 1; i < RP; ++i) {
-        float v = a[tri<RP>(j, i)];
-#pragma unroll
-        for (int l = 0; l < j; ++l) v = __builtin_fmaf(-a[tri<RP>(l, i)], a[tri<RP>(l, j)], v);
-        a[tri<RP>(j, i)] = v * dinv[j];
-      }
-    }
-    // L y = gamma, then L^T delta = y (delta in y)
-#pragma unroll
-    for (int i = 0; i < RP; ++i) {
-      float v = gam[i];
-#pragma unroll
-      for (int l = 0; l < i; ++l) v = __builtin_fmaf(-a[tri<RP>(l, i)], y[l], v);
-      y[i] = v * dinv[i];
-    }
-#pragma unroll
-    for (int i = RP - 1; i >= 0; --i) {
-      float v = y[i];
-#pragma unroll
-      for (int l = i + 1; l < RP; ++l) v = __builtin_fmaf(-a[tri<RP>(i, l)], y[l], v);
-      y[i] = v * dinv[i];
-    }
+    QSC_CHOL_SOLVE(RP, a, mu, !held[j_], gam[i_])
     fl = (ok && idn) ? (fl | FLAG_IDENT) : fl;
     fl = ok ? (fl | FLAG_STEP_OK) : (fl & ~FLAG_STEP_OK);
 #pragma unroll
@@ -465,8 +379,8 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
   if (f_out != nullptr) f_out[k] = w.fc[k];
   if (steps_out != nullptr) steps_out[k] = nwalk;
   if (std_C != nullptr) {
-    // sqrt(diag((J + ridge I)^-1)) at the accepted point: Cholesky, M = L^-1 in place, the
-    // column sums of M^2 (qsc_info_std's steps); the bound is not applied here
+    // sqrt(diag((J + ridge I)^-1)) at the accepted point (qsc_info_std's steps); the bound is not
+    // applied here
     float a[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) a[i] = gjk[RP + i];
@@ -482,37 +396,7 @@ __global__ void __launch_bounds__(kStepBlock) cfit_step_kernel(
     }
     float dinv[RP];
     bool bad = false;
-#pragma unroll
-    for (int j = 0; j < RP; ++j) {
-      float piv = a[tri<RP>(j, j)];
-#pragma unroll
-      for (int i = 0; i < j; ++i) piv = __builtin_fmaf(-a[tri<RP>(i, j)], a[tri<RP>(i, j)], piv);
-      if (!(piv > 0.0f)) {  // (also a NaN block)
-        bad = true;
-        piv = 1.0f;
-      }
-      const float d = sqrtf(piv);
-      dinv[j] = 1.0f / d;
-      a[tri<RP>(j, j)] = d;
-#pragma unroll
-      for (int i = j + 1; i < RP; ++i) {
-        float v = a[tri<RP>(j, i)];
-#pragma unroll
-        for (int l = 0; l < j; ++l) v = __builtin_fmaf(-a[tri<RP>(l, i)], a[tri<RP>(l, j)], v);
-        a[tri<RP>(j, i)] = v * dinv[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RP; ++j) {
-      a[tri<RP>(j, j)] = dinv[j];
-#pragma unroll
-      for (int i = j + 1; i < RP; ++i) {
-        float v = 0.0f;
-#pragma unroll
-        for (int l = j; l < i; ++l) v = __builtin_fmaf(a[tri<RP>(l, i)], a[tri<RP>(j, l)], v);
-        a[tri<RP>(j, i)] = -v * dinv[i];
-      }
-    }
+    QSC_CHOL_INVERSE(RP, a, dinv, bad)
 #pragma unroll
     for (int j = 0; j < RP; ++j) {
       float v = 0.0f;
@@ -548,29 +432,12 @@ int cfit_walk(const qsc_obs_desc* d, const void* c_entries, const int32_t* c_wid
   Edges E;
   make_edges(m, &E);
   const dim3 grid((unsigned)G), blk((unsigned)(64 * std::min(d->nks, kWaves)));
-  const bool sr = d->rowfmt == 1;
-#define CFIT_LAUNCH_E(RPV, ET, SRV, LGT, LOGV, KD)                                              \
+#define CFIT_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                \
   hipLaunchKernelGGL((cfit_eval_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,       \
                      (const ET*)c_entries, c_width, c_off, c_kmap, (int64_t)d->c_entries, d->nks, \
                      d->PT, d->ntiles, G, lk, E, R, d->K, S, w.Ct, w.pf, w.pgj)
-#define CFIT_LAUNCH_RP(RPV, LGT, LOGV, KD)                                  \
-  do {                                                                      \
-    if (sr) {                                                               \
-      /* (signed rows: linear one-bit only) */                              \
-      if (!LOGV) CFIT_LAUNCH_E(RPV, uint16_t, true, LGT, false, KD);        \
-    } else if (d->wide) CFIT_LAUNCH_E(RPV, uint32_t, false, LGT, LOGV, KD); \
-    else CFIT_LAUNCH_E(RPV, uint16_t, false, LGT, LOGV, KD);                \
-  } while (0)
-#define CFIT_LAUNCH(LGT, LOGV, KD)                      \
-  do {                                                  \
-    if (RP == 4) CFIT_LAUNCH_RP(4, LGT, LOGV, KD);      \
-    else if (RP == 8) CFIT_LAUNCH_RP(8, LGT, LOGV, KD); \
-    else CFIT_LAUNCH_RP(16, LGT, LOGV, KD);             \
-  } while (0)
-  QSC_INFO_DISPATCH(CFIT_LAUNCH);
+  QSC_LAYOUT_DISPATCH(CFIT_LAUNCH);
 #undef CFIT_LAUNCH
-#undef CFIT_LAUNCH_RP
-#undef CFIT_LAUNCH_E
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }
@@ -626,8 +493,7 @@ QSC_API int qsc_cfit_begin(const qsc_obs_desc* d, const void* c_entries, const i
                            void* ws, size_t ws_bytes, void* stream) {
   // (the entry array always holds its QSC_ENTRY_TAIL pads, which the walk's read-ahead may touch)
   if (!c_entries || !c_width || !c_off || !c_kmap || !S || !C_init) return QSC_EINVAL;
-  if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
-  if (!(ridge >= 0.0f) || !(mu0 >= 0.0f) || !(tol > 0.0f) || max_steps < 1) return QSC_EINVAL;
+  if (!newton_args_ok(kind, ridge, mu0, tol, max_steps)) return QSC_EINVAL;
   const int rc = cfit_check(d, m, R, ws, ws_bytes);
   if (rc != QSC_OK) return rc;
   const int RP = qsc_rank_pad(R), G = cfit_groups(d, RP);

@@ -618,6 +618,20 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// compute units of the current device (cached per device id)
+inline int cu_count() {
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!cached[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+      n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
 // Signed-row gather tables (include/qsc.h rowfmt 1) of `rows` factor rows: rows [0, rows) hold
 // [+row, +thr'], the negated copies start at row sr_off(rows), a multiple of 16 so that a row
 // and its negation share a bank residue (qsc_sched.cuh), then kSrPadRows neutral pad rows

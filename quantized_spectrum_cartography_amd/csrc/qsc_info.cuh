@@ -1,6 +1,6 @@
-// qsc_info.cuh — the link terms (P, P', P''), the per-entry curvature and the S-format list walk
-// helpers shared by qsc_info.hip (information blocks), qsc_sfit.hip (per-pixel Newton fit of S)
-// and qsc_cfit.hip (per-bin Newton fit of C).
+// qsc_info.cuh — the link terms (P, P', P''), the per-entry curvature and terms, the S-format list
+// decode and the dispatch macros shared by qsc_info.hip (information blocks) and, through
+// qsc_newton.cuh, the Newton fits (qsc_sfit.hip, qsc_cfit.hip, qsc_sfit_smooth.hip).
 // qsc_info.hip's header has the formulas and the numerics.
 //
 // Everything lives in an anonymous namespace on purpose: each translation unit gets its own
@@ -129,8 +129,9 @@ __host__ __device__ __forceinline__ float entry_curvature(float t, int code,
   return h * tinv2;
 }
 
-// ---- the per-entry terms of the Newton fits (qsc_sfit.hip, qsc_cfit.hip) ----
-// One entry's fp32 f, g_t and h at t (see the file header); `use` is false for what adds 0 to g, J.
+// ---- the per-entry terms of the Newton fits (qsc_newton.cuh: QSC_ENTRY_ACCUMULATE) ----
+// One entry's fp32 f, g_t and h at t (qsc_newton.cuh's header); `use` is false for what adds 0 to
+// g and J.
 template <bool LOGIT, bool LOG, int KIND>
 __device__ __forceinline__ void entry_terms(float t, int code, const float2* __restrict__ edges,
                                             const Link& c, float& fe, float& gt, float& h,
@@ -278,19 +279,39 @@ inline bool info_layout_ok(const qsc_obs_desc* d, const qsc_model* m, int R) {
 
 }  // namespace
 
-// dispatch over (link, log model, kind) for LAUNCH(LOGIT, LOG, KIND)
-#define QSC_INFO_DISPATCH(LAUNCH)                                        \
+// dispatch over (link, log model, kind) for APPLY(LAUNCH, LOGIT, LOG, KIND); reads m and kind
+#define QSC_INFO_DISPATCH_(APPLY, LAUNCH)                                \
   do {                                                                   \
     const bool lg_ = m->loss == QSC_LOSS_LOGIT, lo_ = m->log_model != 0; \
     if (kind == INFO_OBSERVED) {                                         \
-      if (lg_ && lo_) LAUNCH(true, true, INFO_OBSERVED);                 \
-      else if (lg_) LAUNCH(true, false, INFO_OBSERVED);                  \
-      else if (lo_) LAUNCH(false, true, INFO_OBSERVED);                  \
-      else LAUNCH(false, false, INFO_OBSERVED);                          \
+      if (lg_ && lo_) APPLY(LAUNCH, true, true, INFO_OBSERVED);          \
+      else if (lg_) APPLY(LAUNCH, true, false, INFO_OBSERVED);           \
+      else if (lo_) APPLY(LAUNCH, false, true, INFO_OBSERVED);           \
+      else APPLY(LAUNCH, false, false, INFO_OBSERVED);                   \
     } else {                                                             \
-      if (lg_ && lo_) LAUNCH(true, true, INFO_EXPECTED);                 \
-      else if (lg_) LAUNCH(true, false, INFO_EXPECTED);                  \
-      else if (lo_) LAUNCH(false, true, INFO_EXPECTED);                  \
-      else LAUNCH(false, false, INFO_EXPECTED);                          \
+      if (lg_ && lo_) APPLY(LAUNCH, true, true, INFO_EXPECTED);          \
+      else if (lg_) APPLY(LAUNCH, true, false, INFO_EXPECTED);           \
+      else if (lo_) APPLY(LAUNCH, false, true, INFO_EXPECTED);           \
+      else APPLY(LAUNCH, false, false, INFO_EXPECTED);                   \
     }                                                                    \
   } while (0)
+#define QSC_INFO_APPLY_(LAUNCH, LGT, LOGV, KD) LAUNCH(LGT, LOGV, KD)
+// ... for LAUNCH(LOGIT, LOG, KIND)
+#define QSC_INFO_DISPATCH(LAUNCH) QSC_INFO_DISPATCH_(QSC_INFO_APPLY_, LAUNCH)
+
+// ... and over the layout for LAUNCH(RP, E, SR, LOGIT, LOG, KIND): rank pad 4 / 8 / 16, narrow /
+// wide / signed-row entries (signed rows: linear one-bit only); reads RP and d as well
+#define QSC_LAYOUT_E_(LAUNCH, RPV, LGT, LOGV, KD)                    \
+  do {                                                               \
+    if (d->rowfmt == 1) {                                            \
+      if (!LOGV) LAUNCH(RPV, uint16_t, true, LGT, false, KD);        \
+    } else if (d->wide) LAUNCH(RPV, uint32_t, false, LGT, LOGV, KD); \
+    else LAUNCH(RPV, uint16_t, false, LGT, LOGV, KD);                \
+  } while (0)
+#define QSC_LAYOUT_RP_(LAUNCH, LGT, LOGV, KD)                    \
+  do {                                                           \
+    if (RP == 4) QSC_LAYOUT_E_(LAUNCH, 4, LGT, LOGV, KD);        \
+    else if (RP == 8) QSC_LAYOUT_E_(LAUNCH, 8, LGT, LOGV, KD);   \
+    else QSC_LAYOUT_E_(LAUNCH, 16, LGT, LOGV, KD);               \
+  } while (0)
+#define QSC_LAYOUT_DISPATCH(LAUNCH) QSC_INFO_DISPATCH_(QSC_LAYOUT_RP_, LAUNCH)

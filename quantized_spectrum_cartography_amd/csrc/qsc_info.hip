@@ -24,25 +24,21 @@
 // contributes exactly 0 to phi and to z phi: no product meets an infinity.  An entry whose P
 // underflows to 0 has no representable curvature and contributes 0.
 //
-// qsc_sinfo walks the S-format lists as the S-pass does: one wave per slice of QSC_SLICE
-// positions, two lanes per position; lane half h takes entries 2h, 2h + 1 of every 4-entry chunk
-// in list order and keeps the upper triangle of its partial block in registers; the halves are
-// added once (a + b is the same bits on both lanes) and each half writes RP / 2 rows of the full
-// symmetric block.  No atomics: the order of every sum is fixed by the packing alone.
+// qsc_sinfo walks the S-format lists as qsc_newton.cuh describes; a lane half keeps the upper
+// triangle of its partial block in registers; the halves are added once and each half writes
+// RP / 2 rows of the full symmetric block.  No atomics: the order of every sum is fixed by the
+// packing alone.
 // qsc_info_std: one thread per position, Cholesky of J_q + ridge I in registers, the triangular
-// inverse in place; std_S from its column norms, std_T[k] = |L^-1 c_k|.
+// inverse in place (QSC_CHOL_INVERSE); std_S from its column norms, std_T[k] = |L^-1 c_k|.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "qsc_common.cuh"
-#include "qsc_info.cuh"
+#include "qsc_newton.cuh"
 
 namespace {
 using namespace qsc;
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 
 template <int RP, typename E, bool SR, bool LOGIT, bool LOG, int KIND>
 __global__ void __launch_bounds__(kBlock) sinfo_kernel(
@@ -50,32 +46,13 @@ __global__ void __launch_bounds__(kBlock) sinfo_kernel(
     int64_t n_ent, int nslices, Link lk, Edges E_, int R, int K, const float* __restrict__ S,
     const float* __restrict__ C, float* __restrict__ J) {
   constexpr int CP = info_pitch(RP);
-  constexpr int NT = RP * (RP + 1) / 2;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Cl = smem;                                             // [K][CP]
-  float2* El = reinterpret_cast<float2*>(Cl + (size_t)K * CP);  // [nbins]
-  for (int i = threadIdx.x; i < K * RP; i += kBlock) {
-    const int k = i / RP, r = i - k * RP;
-    Cl[k * CP + r] = r < R ? C[(int64_t)r * K + k] : 0.0f;
-  }
-  for (int b = threadIdx.x; b < lk.nbins; b += kBlock) El[b] = E_.e[b];
-  __syncthreads();
-
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int l = lane & (QSC_SLICE - 1), h = lane >> 5;
-  const int Ko = sr_off(K);
-  const uint32_t pad_value = SR ? 2u * (uint32_t)Ko : (Ent<E>::kPad << Ent<E>::kBits);
+  constexpr int NT = tri_count(RP);
+  QSC_STAGE_TABLE(RP, CP, K, R, C, lk, E_);
+  QSC_SLANE(E, SR, K);
   for (int s = blockIdx.x * kWaves + wave; s < nslices; s += gridDim.x * kWaves) {
     const int64_t q = (int64_t)s * QSC_SLICE + l;
     float sv[RP];
-#pragma unroll
-    for (int r = 0; r < RP; r += 4) {
-      const float4 x = *reinterpret_cast<const float4*>(S + q * RP + r);
-      sv[r] = x.x;
-      sv[r + 1] = x.y;
-      sv[r + 2] = x.z;
-      sv[r + 3] = x.w;
-    }
+    QSC_ROW_LOAD(RP, sv, S + q * RP)
     float acc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i] = 0.0f;
@@ -94,14 +71,7 @@ __global__ void __launch_bounds__(kBlock) sinfo_kernel(
         bool pad;
         decode<E, SR>(v[e], K, Ko, lk.nbins, k, code, pad);
         float cv[RP];
-#pragma unroll
-        for (int r = 0; r < RP; r += 4) {
-          const float4 x = *reinterpret_cast<const float4*>(Cl + k * CP + r);
-          cv[r] = x.x;
-          cv[r + 1] = x.y;
-          cv[r + 2] = x.z;
-          cv[r + 3] = x.w;
-        }
+        QSC_ROW_LOAD(RP, cv, Cl + k * CP)
         float t = 0.0f;
 #pragma unroll
         for (int r = 0; r < RP; ++r) t = __builtin_fmaf(sv[r], cv[r], t);
@@ -170,14 +140,13 @@ __global__ void __launch_bounds__(kBlock) info_std_kernel(
     for (int i = 0; i < RP; ++i) out[i] = 0.0f;
     if (live) {
       // lower triangle a[i][j], j <= i, at tri(j, i)
-      float a[RP * (RP + 1) / 2];
+      float a[tri_count(RP)];
       const float* Jq = J + q * (RP * RP);
 #pragma unroll
       for (int i = 0; i < RP; ++i) {
 #pragma unroll
         for (int j0 = 0; j0 <= i; j0 += 4) {
-          const float4 x = *reinterpret_cast<const float4*>(Jq + i * RP + j0);
-          const float xs[4] = {x.x, x.y, x.z, x.w};
+          QSC_VEC4(xs, Jq + i * RP + j0);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int j = j0 + e;
@@ -190,41 +159,8 @@ __global__ void __launch_bounds__(kBlock) info_std_kernel(
           }
         }
       }
-      float dinv[RP];  // 1 / L[i][i]
-#pragma unroll
-      for (int j = 0; j < RP; ++j) {
-        float piv = a[tri<RP>(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) piv = __builtin_fmaf(-a[tri<RP>(k, j)], a[tri<RP>(k, j)], piv);
-        if (!(piv > 0.0f)) {  // (also a NaN block)
-          bad = true;
-          piv = 1.0f;
-        }
-        const float d = sqrtf(piv);
-        dinv[j] = 1.0f / d;
-        a[tri<RP>(j, j)] = d;
-#pragma unroll
-        for (int i = j + 1; i < RP; ++i) {
-          float v = a[tri<RP>(j, i)];
-#pragma unroll
-          for (int k = 0; k < j; ++k) v = __builtin_fmaf(-a[tri<RP>(k, i)], a[tri<RP>(k, j)], v);
-          a[tri<RP>(j, i)] = v * dinv[j];
-        }
-      }
-      // M = L^-1 in place, column by column: M[j][j] = 1 / L[j][j],
-      // M[i][j] = -(sum_{k = j}^{i-1} L[i][k] M[k][j]) / L[i][i]   (columns > j still hold L)
-#pragma unroll
-      for (int j = 0; j < RP; ++j) {
-        a[tri<RP>(j, j)] = dinv[j];
-#pragma unroll
-        for (int i = j + 1; i < RP; ++i) {
-          float v = 0.0f;
-#pragma unroll
-          for (int k = j; k < i; ++k) v = __builtin_fmaf(a[tri<RP>(k, i)], a[tri<RP>(j, k)], v);
-          a[tri<RP>(j, i)] = -v * dinv[i];
-        }
-      }
-      // diag(A^-1)[j] = sum_{i >= j} M[i][j]^2
+      float dinv[RP];
+      QSC_CHOL_INVERSE(RP, a, dinv, bad)
 #pragma unroll
       for (int j = 0; j < RP; ++j) {
         float v = 0.0f;
@@ -249,22 +185,11 @@ __global__ void __launch_bounds__(kBlock) info_std_kernel(
         }
       }
     }
-#pragma unroll
-    for (int r = 0; r < RP; r += 4)
-      *reinterpret_cast<float4*>(std_S + q * RP + r) =
-          make_float4(out[r], out[r + 1], out[r + 2], out[r + 3]);
+    QSC_ROW_STORE(RP, std_S + q * RP, out);
   }
   // one integer atomic per wave (integer addition: any order gives the same count)
   const unsigned long long m = __ballot(bad);
   if ((threadIdx.x & 63) == 0 && m != 0ull) atomicAdd(nbad, __popcll(m));
-}
-
-int cu_count_info() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-    return 256;
-  return n;
 }
 
 }  // namespace
@@ -278,15 +203,7 @@ QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_
                       const float* C, int32_t kind, float* J, void* stream) {
   if (!d || !s_width || !s_off || !S || !C || !J || !info_model_ok(m)) return QSC_EINVAL;
   if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
-  if (R < 1 || R > QSC_MAX_R || d->K < 1 || d->P < 1 || d->Pp < d->P || (d->Pp % 64) != 0 ||
-      d->nbins != m->nbounds - 1 || d->s_entries < 0 || (d->s_entries > 0 && !s_entries))
-    return QSC_EINVAL;
-  if (d->rowfmt != 0 && d->rowfmt != 1) return QSC_EINVAL;
-  // signed rows: the one-bit layout, narrow entries, every row index representable
-  if (d->rowfmt == 1 && (d->wide || d->nbins != 2 || (int64_t)sr_rows(d->K) > 0x10000))
-    return QSC_EINVAL;
-  if (!d->wide && d->rowfmt == 0 && (d->K > 4096 || d->nbins > 15)) return QSC_EINVAL;
-  if (d->wide && d->K > (1 << 24)) return QSC_EINVAL;
+  if (!info_layout_ok(d, m, R) || (d->s_entries > 0 && !s_entries)) return QSC_EINVAL;
   const int RP = qsc_rank_pad(R);
   const size_t shm = sinfo_lds(d->K, RP, d->nbins);
   if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
@@ -294,35 +211,14 @@ QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_
   Edges E;
   make_edges(m, &E);
   const int nslices = d->Pp / QSC_SLICE;
-  // a grid-stride walk over the slices (any grid gives the same bits): enough workgroups to fill
-  // the device, few enough that the C^T staging stays a small part of the traffic
-  const int64_t want = ceil_div(nslices, kWaves);
-  const dim3 grid((unsigned)std::min<int64_t>(want, (int64_t)cu_count_info() * 8)), blk(kBlock);
+  const dim3 grid((unsigned)slice_grid(nslices, 8)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
-  const bool sr = d->rowfmt == 1;
-#define SINFO_LAUNCH_E(RPV, ET, SRV, LGT, LOGV, KD)                                              \
+#define SINFO_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                \
   hipLaunchKernelGGL((sinfo_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,            \
                      (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
                      R, d->K, S, C, J)
-#define SINFO_LAUNCH_RP(RPV, LGT, LOGV, KD)                                  \
-  do {                                                                       \
-    if (sr) {                                                                \
-      /* (signed rows: linear one-bit only) */                               \
-      if (!LOGV) SINFO_LAUNCH_E(RPV, uint16_t, true, LGT, false, KD);        \
-    } else if (d->wide) SINFO_LAUNCH_E(RPV, uint32_t, false, LGT, LOGV, KD); \
-    else SINFO_LAUNCH_E(RPV, uint16_t, false, LGT, LOGV, KD);                \
-  } while (0)
-#define SINFO_LAUNCH(LGT, LOGV, KD)                      \
-  do {                                                   \
-    if (RP == 4) SINFO_LAUNCH_RP(4, LGT, LOGV, KD);      \
-    else if (RP == 8) SINFO_LAUNCH_RP(8, LGT, LOGV, KD); \
-    else SINFO_LAUNCH_RP(16, LGT, LOGV, KD);             \
-  } while (0)
-  if (sr && m->log_model) return QSC_EINVAL;
-  QSC_INFO_DISPATCH(SINFO_LAUNCH);
+  QSC_LAYOUT_DISPATCH(SINFO_LAUNCH);
 #undef SINFO_LAUNCH
-#undef SINFO_LAUNCH_RP
-#undef SINFO_LAUNCH_E
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }

@@ -121,20 +121,6 @@ void set_dbg(Lik& lk, const qsc_obs_desc* d, bool sr) {
   lk.dbg_ent[1] = d->c_entries;
 }
 
-// compute units of the current device (cached per device id)
-int cu_count() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cached[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
 // resident S-pass workgroups per CU (persistent grid); RP=16 needs twice the registers
 #ifndef QSC_SPASS_BPC
 #define QSC_SPASS_BPC 2
