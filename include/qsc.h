@@ -810,6 +810,56 @@ QSC_API int qsc_map_compose(const float* shadow, const float* loc, const float* 
                             int32_t I, int32_t J, float res, float d0, int32_t db, float* S,
                             float* norms, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Observation packing from a LIST of readings (csrc/qsc_obs_readings.hip): device arrays k[n],
+ * p[n] (int32, pixel p = i*J + j) and code[n] (uint8 when code_bytes = 1, int32 when 4),
+ * 1 <= n < 2^31, in any order; a cell (k, p) may be read any number of times, and every reading
+ * is one independent observation.  The result is the packing of qsc_obs_desc above, filled from
+ * the list instead of a dense codes[K][P]:
+ *   - without repeated cells every output (cnt, s_width, s_off, c_width, c_off, c_kmap, *desc,
+ *     s_entries, c_entries) is bit-identical to qsc_obs_count / _layout / _fill on the equivalent
+ *     codes, whatever the order of the list;
+ *   - with repeats, a position's S-format list holds its readings in ascending k and a (tile,
+ *     bin) C-format list in ascending qlocal, equal keys in the order of the list (stable); bin
+ *     order and widths follow from the counts of READINGS by the rules above; desc->nnz counts
+ *     readings;
+ *   - integer atomics are used for counts only: the packed bytes are a function of the list.
+ * Sequence: qsc_obs_readings_count -> (qsc_obs_order, or a caller's perm) ->
+ * qsc_obs_readings_layout -> qsc_obs_readings_fill -> (qsc_obs_schedule, unchanged).
+ * ------------------------------------------------------------------------------------- */
+/* cnt[p] = number of in-range readings of pixel p (zeroed here), and *bad (device int32, the
+ * caller zeroes it) += the number of readings with k outside [0,K), p outside [0,P) or code
+ * outside [0,nbins).  Nothing is ever packed from such a reading; callers raise on *bad != 0. */
+QSC_API int qsc_obs_readings_count(const int32_t* k, const int32_t* p, const void* code,
+                                   int32_t code_bytes, int64_t n, int32_t K, int32_t P,
+                                   int32_t nbins, int32_t* cnt, int32_t* bad, void* stream);
+/* bytes of `packed`, the sorted readings the caller keeps for qsc_obs_readings_fill (8 n plus
+ * the segment tables: 4 (Pp + 1) + 8 ntiles 64 nks), and of the layout call's workspace (32 n
+ * for the sort keys and values, the radix sort's own buffers, and the count tables); 0 for
+ * arguments out of range */
+QSC_API size_t qsc_obs_readings_packed_bytes(int64_t n, int32_t K, int32_t P, int32_t PT);
+QSC_API size_t qsc_obs_readings_workspace_bytes(int64_t n, int32_t K, int32_t P, int32_t PT);
+/* SYNCHRONOUS (as qsc_obs_layout: reads the totals): sorts the readings into both formats'
+ * orders (-> packed), computes widths, offsets and the C-format bin order, and fills *desc
+ * (rowfmt 0; nnz = the in-range readings).  perm must be a permutation of the pixels over the
+ * Pp positions (-1 = padding), cnt the output of qsc_obs_readings_count.  *max_repeat (HOST
+ * pointer, may be NULL) receives the largest number of readings of one cell.  K and PT must be
+ * below 2^24 and ntiles * 64 nks below 2^31. */
+QSC_API int qsc_obs_readings_layout(const int32_t* k, const int32_t* p, const void* code,
+                                    int32_t code_bytes, int64_t n, int32_t K, int32_t P,
+                                    int32_t PT, int32_t nbins, const int32_t* perm,
+                                    const int32_t* cnt, int32_t* s_width, int64_t* s_off,
+                                    int32_t* c_width, int64_t* c_off, int32_t* c_kmap,
+                                    void* packed, size_t packed_bytes, void* ws, size_t ws_bytes,
+                                    qsc_obs_desc* desc, int32_t* max_repeat, void* stream);
+/* qsc_obs_fill's counterpart: writes s_entries / c_entries in the format desc->rowfmt from
+ * `packed` (asynchronous; may be called again with another rowfmt and other entry arrays). */
+QSC_API int qsc_obs_readings_fill(const void* packed, size_t packed_bytes, int64_t n,
+                                  const qsc_obs_desc* desc, const int32_t* s_width,
+                                  const int64_t* s_off, const int32_t* c_width,
+                                  const int64_t* c_off, const int32_t* c_kmap, void* s_entries,
+                                  void* c_entries, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libqsc_hip.so")
 # the fused passes (qsc_pass.cuh), one translation unit per kernel family so that they compile
 # side by side
 PASS_SOURCES = ["qsc_pass_s.hip", "qsc_pass_c.hip", "qsc_pass_fused.hip", "qsc_pass_finish.hip"]
-SOURCES = PASS_SOURCES + ["qsc_ops.hip", "qsc_obs.hip", "qsc_gram.hip", "qsc_spa.hip",
+SOURCES = PASS_SOURCES + ["qsc_ops.hip", "qsc_obs.hip", "qsc_obs_readings.hip", "qsc_gram.hip", "qsc_spa.hip",
                           "qsc_map.hip", "qsc_smooth.hip", "qsc_info.hip", "qsc_sfit.hip", "qsc_cfit.hip",
                           "qsc_sfit_smooth.hip"]
 ARCH = os.environ.get("QSC_OFFLOAD_ARCH", "gfx950")

@@ -6,6 +6,7 @@ into uint8 codes (0xFF = unobserved), then packs only the observed entries into 
 sliced formats of include/qsc.h (one per pass), with pixels re-ordered by observation count
 so that the 64 lanes of every wavefront carry near-equal work.  Built once per solve.
 """
+import ctypes
 import os
 
 import torch
@@ -96,6 +97,38 @@ class Observations:
                  tile=None, R_hint=8, count_hook=None, loss="probit", schedule=None):
         K = Y.shape[0]
         I, J = Y.shape[-2], Y.shape[-1]
+        PT, nbins = self._setup(K, I, J, bin_boundaries, noise_std, offset, log_model, tile,
+                                R_hint, loss, schedule)
+        P = self.P
+        Yd = _dev(Y.reshape(K, P).to(torch.int64))
+        dev = Yd.device
+        self.device = dev
+        Wd = _dev(Wx.reshape(K, P).to(torch.float32)) if Wx is not None else None
+        codes = torch.empty((K, P), dtype=torch.uint8, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.call("qsc_pack_codes", _lib.ptr(Yd), _lib.ptr(Wd), K * P, nbins, _lib.ptr(codes),
+                  _lib.ptr(bad), _lib.stream())
+        nbad = int(bad.item())
+        if nbad:
+            raise ValueError("%d observed entries have a code outside [0, %d) or a sampling "
+                             "weight other than 0/1" % (nbad, nbins))
+        self.codes = codes
+        s = _lib.stream()
+        cnt = torch.empty(P, dtype=torch.int32, device=dev)
+        _lib.call("qsc_obs_count", _lib.ptr(codes), K, P, _lib.ptr(cnt), s)
+        self.counts = cnt
+        perm = self._order(cnt, perm, count_hook)
+        self._alloc_tables(PT)
+        desc = _lib.QscObsDesc()
+        ws = _ws(_lib.lib().qsc_obs_layout_workspace_bytes(K, P, PT), dev)
+        _lib.call("qsc_obs_layout", _lib.ptr(codes), K, P, PT, nbins, _lib.ptr(perm), _lib.ptr(cnt),
+                  _lib.ptr(self.s_width), _lib.ptr(self.s_off), _lib.ptr(self.c_width),
+                  _lib.ptr(self.c_off), _lib.ptr(self.c_kmap), _lib.ptr(ws), ws.numel(), desc, s)
+        self._finish(desc, R_hint)
+
+    def _setup(self, K, I, J, bin_boundaries, noise_std, offset, log_model, tile, R_hint, loss,
+               schedule):
+        """The part of construction that needs no device: shape, tile, model.  -> (PT, nbins)"""
         P = I * J
         if schedule is None:  # QSC_SCHEDULE=0: natural list order (A/B switch)
             schedule = os.environ.get("QSC_SCHEDULE", "1") != "0"
@@ -116,23 +149,11 @@ class Observations:
         nbins = len(self.bin_boundaries) - 1
         if nbins > 254:
             raise ValueError("at most 254 bins are supported (code 0xFF marks unobserved)")
-        Yd = _dev(Y.reshape(K, P).to(torch.int64))
-        dev = Yd.device
-        self.device = dev
-        Wd = _dev(Wx.reshape(K, P).to(torch.float32)) if Wx is not None else None
-        codes = torch.empty((K, P), dtype=torch.uint8, device=dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.call("qsc_pack_codes", _lib.ptr(Yd), _lib.ptr(Wd), K * P, nbins, _lib.ptr(codes),
-                  _lib.ptr(bad), _lib.stream())
-        nbad = int(bad.item())
-        if nbad:
-            raise ValueError("%d observed entries have a code outside [0, %d) or a sampling "
-                             "weight other than 0/1" % (nbad, nbins))
-        self.codes = codes
-        s = _lib.stream()
-        cnt = torch.empty(P, dtype=torch.int32, device=dev)
-        _lib.call("qsc_obs_count", _lib.ptr(codes), K, P, _lib.ptr(cnt), s)
-        self.counts = cnt
+        return PT, nbins
+
+    def _order(self, cnt, perm, count_hook):
+        """The pixel order: by observation count (qsc_obs_order), or the caller's perm."""
+        dev, P = self.device, self.P
         if perm is None:
             # count_hook (e.g. an all-reduce over K-slab ranks) makes the pixel order a function
             # of the global counts, so every rank lays S out identically
@@ -146,17 +167,19 @@ class Observations:
             if perm.numel() != self.Pp:
                 raise ValueError("perm must have Pp = %d entries" % self.Pp)
         self.perm = perm
-        ns, nt, nks = self.Pp // _lib.QSC_SLICE, self.Pp // PT, -(-K // 64)
+        return perm
+
+    def _alloc_tables(self, PT):
+        dev = self.device
+        ns, nt, nks = self.Pp // _lib.QSC_SLICE, self.Pp // PT, -(-self.K // 64)
         self.s_width = torch.empty(ns, dtype=torch.int32, device=dev)
         self.s_off = torch.empty(ns + 1, dtype=torch.int64, device=dev)
         self.c_width = torch.empty(nt * nks, dtype=torch.int32, device=dev)
         self.c_off = torch.empty(nt * nks + 1, dtype=torch.int64, device=dev)
         self.c_kmap = torch.empty(nt * nks * 64, dtype=torch.int32, device=dev)
-        desc = _lib.QscObsDesc()
-        ws = _ws(_lib.lib().qsc_obs_layout_workspace_bytes(K, P, PT), dev)
-        _lib.call("qsc_obs_layout", _lib.ptr(codes), K, P, PT, nbins, _lib.ptr(perm), _lib.ptr(cnt),
-                  _lib.ptr(self.s_width), _lib.ptr(self.s_off), _lib.ptr(self.c_width),
-                  _lib.ptr(self.c_off), _lib.ptr(self.c_kmap), _lib.ptr(ws), ws.numel(), desc, s)
+
+    def _finish(self, desc, R_hint):
+        dev = self.device
         self.desc = desc
         et = torch.int32 if desc.wide else torch.int16
         self.s_entries = torch.empty(desc.s_entries, dtype=et, device=dev)
@@ -167,6 +190,106 @@ class Observations:
         # through the gathered row) wherever the passes' doubled tables fit at this rank
         self._fill(rowfmt)
 
+    @staticmethod
+    def check_readings(k, i, j, code, shape, tile=None):
+        """Host-side checks of a list of readings, before any device call: four 1-D integer
+        tensors of one length n >= 1, shape = (K, I, J) positive, tile a multiple of 64.
+        -> (K, I, J, n).  Raises ValueError."""
+        try:
+            K, I, J = (int(x) for x in shape)
+        except (TypeError, ValueError):
+            raise ValueError("shape must be (K, I, J), got %r" % (shape,))
+        if K < 1 or I < 1 or J < 1 or I * J >= 2 ** 31:
+            raise ValueError("shape (K, I, J) must be positive with I * J < 2^31, got %r"
+                             % (shape,))
+        if tile is not None and (int(tile) < 64 or int(tile) % 64):
+            raise ValueError("tile must be a positive multiple of 64")
+        ints = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+        for name, t in (("k", k), ("i", i), ("j", j), ("code", code)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1:
+                raise ValueError("%s must be a 1-D tensor" % name)
+            if t.dtype not in ints:
+                raise ValueError("%s must have an integer dtype, got %s" % (name, t.dtype))
+        n = k.numel()
+        if not (i.numel() == j.numel() == code.numel() == n):
+            raise ValueError("k, i, j and code must have one length, got %d, %d, %d, %d"
+                             % (n, i.numel(), j.numel(), code.numel()))
+        if n < 1:
+            raise ValueError("need at least one reading")
+        if n >= 2 ** 31:
+            raise ValueError("at most 2^31 - 1 readings are supported, got %d" % n)
+        return K, I, J, n
+
+    @classmethod
+    def from_readings(cls, k, i, j, code, shape, bin_boundaries, noise_std, offset=0.0,
+                      log_model=False, perm=None, tile=None, R_hint=8, count_hook=None,
+                      loss="probit", schedule=None):
+        """Packed observations from a list of readings: reading e says that bin k[e] at pixel
+        (i[e], j[e]) of the shape = (K, I, J) map was observed with code code[e].  The four 1-D
+        integer tensors may be in any order, and a cell may be read any number of times: every
+        reading is one independent observation (its likelihood term is added).  The other
+        arguments are the constructor's.  Packing is qsc_obs_readings_* (include/qsc.h): its cost
+        follows the number of readings, not K I J, and no dense array is formed; without
+        repeated cells the result is bit-identical to the constructor's on the equivalent Y, Wx.
+        On the result `codes` is None, `counts` the per-pixel number of readings, `nnz` the
+        number of readings, and stats() gains max_repeat.
+        Raises ValueError for lists of unequal length, non-integer dtypes, no readings, a shape
+        or tile out of range (before any device call), and with the number of readings whose k,
+        (i, j) or code is out of range."""
+        K, I, J, n = cls.check_readings(k, i, j, code, shape, tile)
+        self = cls.__new__(cls)
+        PT, nbins = self._setup(K, I, J, bin_boundaries, noise_std, offset, log_model, tile,
+                                R_hint, loss, schedule)
+        P = self.P
+        # (values past int32 stay out of range instead of wrapping into it)
+        kd = _dev(k).to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+        dev = kd.device
+        self.device = dev
+        # p = i J + j in int64 with out-of-grid (i, j) mapped to -1 (counted by the device)
+        i64, j64 = _dev(i).to(torch.int64), _dev(j).to(torch.int64)
+        inside = (i64 >= 0) & (i64 < I) & (j64 >= 0) & (j64 < J)
+        pd = torch.where(inside, i64 * J + j64, torch.full_like(i64, -1)).to(torch.int32)
+        cd = _dev(code)
+        cd = (cd if cd.dtype == torch.uint8 else
+              cd.to(torch.int64).clamp(-1, 1 << 20).to(torch.int32)).contiguous()
+        cb = 1 if cd.dtype == torch.uint8 else 4
+        s = _lib.stream()
+        cnt = torch.empty(P, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.call("qsc_obs_readings_count", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, n, K, P,
+                  nbins, _lib.ptr(cnt), _lib.ptr(bad), s)
+        nbad = int(bad.item())
+        if nbad:
+            raise ValueError("%d of %d readings have k outside [0, %d), (i, j) outside the "
+                             "%d x %d grid or a code outside [0, %d)" % (nbad, n, K, I, J, nbins))
+        self.codes = None
+        self.counts = cnt
+        perm = self._order(cnt, perm, count_hook)
+        self._alloc_tables(PT)
+        L = _lib.lib()
+        nb = L.qsc_obs_readings_packed_bytes(n, K, P, PT)
+        wb = L.qsc_obs_readings_workspace_bytes(n, K, P, PT)
+        if nb == 0 or wb == 0:
+            raise ValueError("the shape %r with tile %d is out of the packing's range"
+                             % ((K, I, J), PT))
+        self._packed = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self._n = n
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)  # (32 n: not kept in the ws cache)
+        desc = _lib.QscObsDesc()
+        rep = ctypes.c_int32(0)
+        _lib.call("qsc_obs_readings_layout", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, n, K, P,
+                  PT, nbins, _lib.ptr(perm), _lib.ptr(cnt), _lib.ptr(self.s_width),
+                  _lib.ptr(self.s_off), _lib.ptr(self.c_width), _lib.ptr(self.c_off),
+                  _lib.ptr(self.c_kmap), _lib.ptr(self._packed), nb, _lib.ptr(ws), wb, desc,
+                  ctypes.byref(rep), s)
+        del ws
+        if int(desc.nnz) != n:  # a caller's perm that gives some read pixel no position
+            raise ValueError("perm places only %d of the %d readings: every pixel that has a "
+                             "reading needs a position" % (int(desc.nnz), n))
+        self.max_repeat = int(rep.value)
+        self._finish(desc, R_hint)
+        return self
+
     def _fill(self, rowfmt, desc=None, s_entries=None, c_entries=None):
         """Pack the entries in format `rowfmt` into (desc, s_entries, c_entries) (default: this
         object's own arrays; only before any pass engine uses them, see layout())."""
@@ -176,10 +299,16 @@ class Observations:
                                    "captured hipGraph): re-packing them in place is refused")
             desc, s_entries, c_entries = self.desc, self.s_entries, self.c_entries
         desc.rowfmt = int(rowfmt)
-        _lib.call("qsc_obs_fill", _lib.ptr(self.codes), desc, _lib.ptr(self.perm),
-                  _lib.ptr(self.s_width), _lib.ptr(self.s_off), _lib.ptr(self.c_width),
-                  _lib.ptr(self.c_off), _lib.ptr(self.c_kmap), _lib.ptr(s_entries),
-                  _lib.ptr(c_entries), _lib.stream())
+        if self.codes is None:  # from_readings: from the kept sorted readings, no dense codes
+            _lib.call("qsc_obs_readings_fill", _lib.ptr(self._packed), self._packed.numel(),
+                      self._n, desc, _lib.ptr(self.s_width), _lib.ptr(self.s_off),
+                      _lib.ptr(self.c_width), _lib.ptr(self.c_off), _lib.ptr(self.c_kmap),
+                      _lib.ptr(s_entries), _lib.ptr(c_entries), _lib.stream())
+        else:
+            _lib.call("qsc_obs_fill", _lib.ptr(self.codes), desc, _lib.ptr(self.perm),
+                      _lib.ptr(self.s_width), _lib.ptr(self.s_off), _lib.ptr(self.c_width),
+                      _lib.ptr(self.c_off), _lib.ptr(self.c_kmap), _lib.ptr(s_entries),
+                      _lib.ptr(c_entries), _lib.stream())
         if self.schedule:
             # bank-conflict-free list order (include/qsc.h qsc_obs_schedule): the same order for
             # both entry formats (it depends only on the row residues), so their results agree
@@ -222,11 +351,14 @@ class Observations:
 
     def stats(self):
         d = self.desc
-        return dict(K=d.K, P=d.P, Pp=d.Pp, tile=d.PT, ntiles=d.ntiles, nks=d.nks, wide=d.wide,
-                    nbins=d.nbins, nnz=d.nnz, s_entries=d.s_entries, c_entries=d.c_entries,
-                    rowfmt=d.rowfmt,
-                    s_padding=d.s_entries / max(d.nnz, 1) - 1.0,
-                    c_padding=d.c_entries / max(d.nnz, 1) - 1.0)
+        out = dict(K=d.K, P=d.P, Pp=d.Pp, tile=d.PT, ntiles=d.ntiles, nks=d.nks, wide=d.wide,
+                   nbins=d.nbins, nnz=d.nnz, s_entries=d.s_entries, c_entries=d.c_entries,
+                   rowfmt=d.rowfmt,
+                   s_padding=d.s_entries / max(d.nnz, 1) - 1.0,
+                   c_padding=d.c_entries / max(d.nnz, 1) - 1.0)
+        if self.codes is None:  # from_readings: the largest number of readings of one cell
+            out["max_repeat"] = self.max_repeat
+        return out
 
     # ---- order conversions -------------------------------------------------------------
     def rank_pad(self, R):

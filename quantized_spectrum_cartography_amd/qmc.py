@@ -1003,7 +1003,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
-          confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0):
+          confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0, obs_holdout=None):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -1071,8 +1071,27 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     refuses.  result.polish_smooth is the FitSSmoothResult (without S).  Raises ValueError with
     smooth = 0, with a generator and with loss="squared".  The default 0 leaves every path and
     result bit-identical.
+    obs= gives the packed observations (an Observations, e.g. Observations.from_readings for a
+    list of sensor reports); Y and Wx may then be None, and K, I, J, the model and the loss are
+    obs's.  obs_holdout= (with obs=, free S only) is a second Observations packed with obs.perm and
+    obs's tile: the run then early-stops on its NLL exactly as holdout > 0 does on the entries it
+    splits off itself (solve_readings(holdout=...) splits a list of readings this way).  Its loss
+    and model (bin boundaries, noise_std, offset, log_model) must be obs's.
     Returns a SolveResult with S (R,1,I,J) and C (R,K) on the GPU.
     """
+    if Y is None and obs is None:
+        raise ValueError("Y=None needs obs=: the packed observations (Observations, "
+                         "Observations.from_readings)")
+    if obs_holdout is not None:
+        if obs is None or generator is not None:
+            raise ValueError("obs_holdout goes with obs= and free S")
+        if (obs_holdout.Pp != obs.Pp or obs_holdout.desc.PT != obs.desc.PT
+                or obs_holdout.K != obs.K or not torch.equal(obs_holdout.perm, obs.perm)):
+            raise ValueError("obs_holdout must be packed with obs.perm and obs's tile")
+        if any(getattr(obs_holdout, a) != getattr(obs, a)
+               for a in ("loss", "log_model", "noise_std", "offset", "bin_boundaries")):
+            raise ValueError("obs_holdout must carry obs's loss and model (bin boundaries, "
+                             "noise_std, offset, log_model)")
     smooth = check_smooth(smooth, smooth_kind, smooth_delta)
     if smooth > 0.0 and generator is not None:
         raise ValueError("smooth > 0 applies to free S only: a generator already carries the "
@@ -1091,15 +1110,19 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         offset = LOG_OFFSET if offset is None else float(offset)
         if not offset > 0.0:
             raise ValueError("the log model needs offset > 0 (log(T_hat + offset) at T_hat = 0)")
-    K = Y.shape[0]
-    I, J = Y.shape[-2], Y.shape[-1]
+    if Y is None:
+        K, I, J = obs.K, obs.I, obs.J
+    else:
+        K = Y.shape[0]
+        I, J = Y.shape[-2], Y.shape[-1]
     if R is None:
         R = (S_init.shape[0] if S_init is not None else
              (C_init.shape[0] if C_init is not None else Z_init.shape[0]))
-    obs_h = None
-    if holdout and generator is None:
+    obs_h = obs_holdout
+    if holdout and generator is None and obs_h is None:
         if obs is not None:
-            raise ValueError("holdout splits the observations itself: pass Y, Wx, not obs")
+            raise ValueError("holdout splits the observations itself: pass Y, Wx, not obs (or "
+                             "split a list of readings with solve_readings)")
         Wx_fit, Wx_h = split_holdout(Y, Wx, float(holdout), holdout_seed)
         obs = Observations(Y, Wx_fit, bin_boundaries, noise_std, offset=offset or 0.0,
                            log_model=log_model, tile=tile, R_hint=R, loss=loss)
@@ -1396,6 +1419,70 @@ def split_holdout(Y, Wx, frac, seed=0):
     u = torch.rand(W.shape, generator=g).to(W.device)
     hold = (W > 0) & (u < frac)
     return W * (~hold).to(W.dtype), W * hold.to(W.dtype)
+
+
+def split_readings(n, frac, seed=0):
+    """(fit, held): two int64 index tensors that partition range(n), `held` a seeded random
+    round(frac n) of the readings (at least one of each part), both ascending so that each part
+    keeps the list's order.  The same (n, frac, seed) gives the same split."""
+    n = int(n)
+    if not 0.0 < float(frac) < 1.0:
+        raise ValueError("the held-out fraction must be in (0, 1)")
+    if n < 2:
+        raise ValueError("need at least two readings to hold some out")
+    g = torch.Generator().manual_seed(int(seed))
+    order = torch.randperm(n, generator=g)
+    nh = min(max(int(round(float(frac) * n)), 1), n - 1)
+    return torch.sort(order[nh:]).values, torch.sort(order[:nh]).values
+
+
+def solve_readings(k, i, j, code, shape, bin_boundaries, noise_std, R=None, offset=None,
+                   log_model=False, tile=None, loss="probit", holdout=0.0, holdout_seed=0,
+                   **solve_kw):
+    """solve() on a list of readings (see Observations.from_readings: reading e = bin k[e] at
+    pixel (i[e], j[e]) of the shape = (K, I, J) map observed with code code[e]; any order, a cell
+    may be read any number of times).  The readings are packed without a dense Y / Wx and handed
+    to solve(obs=...); solve_kw are solve's other keywords (S_init, C_init, max_iter, use_graph,
+    smooth, confidence, polish_*, ...).  holdout > 0 holds out that fraction of the READINGS
+    (split_readings, seeded by holdout_seed; a cell read three times may keep two readings in the
+    fit and lend one to the check), packs them with the fit part's pixel order and tile, and
+    early-stops on their NLL as solve(holdout=...) does.  The result gains `obs` (and
+    `obs_holdout`, `fit_index`, `held_index` with a holdout)."""
+    for name in ("obs", "obs_holdout", "generator", "Z_init"):
+        if solve_kw.get(name) is not None:
+            raise ValueError("solve_readings packs the readings itself and fits free S: %s= is "
+                             "not accepted" % name)
+    K, I, J, n = Observations.check_readings(k, i, j, code, shape, tile)
+    if R is None:
+        init = solve_kw.get("S_init") if solve_kw.get("S_init") is not None else \
+            solve_kw.get("C_init")
+        if init is None:
+            raise ValueError("give R, S_init or C_init")
+        R = init.shape[0]
+    if log_model:
+        offset = LOG_OFFSET if offset is None else float(offset)
+        if not offset > 0.0:
+            raise ValueError("the log model needs offset > 0 (log(T_hat + offset) at T_hat = 0)")
+    kw = dict(offset=offset or 0.0, log_model=log_model, R_hint=R, loss=loss)
+    if not holdout:
+        obs = Observations.from_readings(k, i, j, code, (K, I, J), bin_boundaries, noise_std,
+                                         tile=tile, **kw)
+        res = solve(None, None, bin_boundaries, noise_std, R=R, obs=obs, **solve_kw)
+        res.obs = obs
+        return res
+    fit, held = split_readings(n, float(holdout), holdout_seed)
+    fit_d, held_d = fit.to(k.device), held.to(k.device)
+    obs = Observations.from_readings(k[fit_d], i[fit_d], j[fit_d], code[fit_d], (K, I, J),
+                                     bin_boundaries, noise_std, tile=tile, **kw)
+    # the held-out readings in the SAME position order (perm) and tiles, so the solver's
+    # position-order S is evaluated on them as it is
+    obs_h = Observations.from_readings(k[held_d], i[held_d], j[held_d], code[held_d], (K, I, J),
+                                       bin_boundaries, noise_std, tile=obs.desc.PT,
+                                       perm=obs.perm, **kw)
+    res = solve(None, None, bin_boundaries, noise_std, R=R, obs=obs, obs_holdout=obs_h,
+                **solve_kw)
+    res.obs, res.obs_holdout, res.fit_index, res.held_index = obs, obs_h, fit, held
+    return res
 
 
 def _solve_holdout(obs, obs_h, S_init, C_init, R, lambda_c, lambda_s, lr_c, lr_s, max_iter,
