@@ -860,6 +860,105 @@ QSC_API int qsc_obs_readings_fill(const void* packed, size_t packed_bytes, int64
                                   const int64_t* c_off, const int32_t* c_kmap, void* s_entries,
                                   void* c_entries, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Calibration of the quantiser: Newton / Fisher-scoring fit of the noise scale and of a common
+ * shift of the levels, for known S and C (qsc_qfit.hip).  Not in the reference, which hard-codes
+ * sigma.
+ *   Two parameters theta = (tau, beta):
+ *     scale  sigma = sigma0 e^tau, sigma0 = m->sigma (for QSC_LOSS_LOGIT the logistic scale); it
+ *            acts through the link's divisor a = fp32(a0 e^tau), a0 = sigma0 * 1.414213 (probit)
+ *            or sigma0 (logit): what a model packed with sigma0 e^tau gives;
+ *     shift  every interior, finite edge becomes fp32(b_i + beta).  In the linear model the two
+ *            clamp edges (-1e5, +1e5) are not shifted; in the log model every finite raw edge is
+ *            and infinite ones stay (there the shift is a common gain).
+ *   Given S and C the fit minimises
+ *     F(theta) = sum_{packed entries} -log max(P(code | x; a, edges), FLT_MIN)
+ *                + prior_scale / 2 tau^2 + prior_shift / 2 beta^2
+ *   with x = t or log(t + offset), t = S[q] . c_k, and P exactly qsc_sinfo's (the same mirroring
+ *   and saturation rules).  Per entry, with u = (hi - x) / a, w = (lo - x) / a on the shifted edges,
+ *   psi the link's density in z-units (probit exp(-z^2) / sqrt(pi), logit F (1 - F)),
+ *   du/dtau = -u and du/dbeta = 1 / a (0 for an unshifted edge):
+ *     P_tau  = -(u psi(u) - w psi(w))               P_beta = (psi(u) - psi(w)) / a
+ *     P_tt   = (z psi + z^2 psi')(u) - (...)(w)     P_tb   = -((psi + z psi')(u) - (...)(w)) / a
+ *     P_bb   = (psi'(u) - psi'(w)) / a^2
+ *     g_i = -P_i / P
+ *     QSC_INFO_OBSERVED:  H_ij = P_i P_j / P^2 - P_ij / P at the entry's own code
+ *     QSC_INFO_EXPECTED:  H_ij = sum_b P_i,b P_j,b / P_b over all bins, bins with P_b == 0
+ *                         dropped: positive semidefinite (the default of qmc.fit_noise)
+ *   A saturated or infinite edge contributes exactly 0 to psi, z psi and z^2 psi'; an entry whose
+ *   fp32 P is 0 adds 0 to g and H and -log FLT_MIN to F; in the log model t + offset <= 0 makes
+ *   F = +inf; a pad entry adds exactly 0.  f is fp64 per entry (from the fp32 S, C and edges, as
+ *   qsc_sfit forms it), g and H fp32 per entry; all sums are fp64.
+ *   An evaluation is a walk (qsc_sinfo's, over the S-format lists of any layout qsc_obs_fill /
+ *   qsc_obs_readings_fill produces; it reads the trial theta from the device-resident state and
+ *   forms its link and shifted edges itself) that leaves one partial of 6 doubles per slice of
+ *   QSC_SLICE positions -- each lane adds its entries in list order, the two halves of a position
+ *   are added, then the 32 positions with the butterfly xor 16, 8, 4, 2, 1 -- and a step of one
+ *   workgroup: thread i of 256 adds the partials of slices i, i + 256, ... in ascending order, the
+ *   thread sums are folded i += i + w for w = 128, 64, ..., 1 (an order fixed by the number of
+ *   slices alone); then, in fp64,
+ *     accept iff F' <= F and F' is finite: theta <- theta', mu <- max(mu / 10, mu0 == 0 ? 0 : mu_min)
+ *     else mu <- max(10 mu, mu_min)                                          mu_min = 1e-6
+ *     converged once an accepted step has |theta' - theta|_inf <= tol (1 + |theta|_inf)
+ *     solve (H + diag(prior) + mu I) delta = g + prior * theta, a parameter outside fit_mask an
+ *       identity row (delta = 0);  theta' = theta - delta
+ *     a pivot that is not positive: the step counts as rejected; a pivot <= mu at every step:
+ *       unidentified (qsc_sfit's rule)
+ *   The calls (qsc_cfit's sequence):
+ *     qsc_qfit_begin     state <- (tau0, beta0), mu0 and the parameters;  walk at the start
+ *     qsc_qfit_iterate   one step, then the walk at the new trial (call it up to max_steps times;
+ *                        a converged or exhausted fit no longer changes)
+ *     qsc_qfit_finish    accepts or rejects the last walked trial and writes the results
+ *   Every call is stream-ordered, never allocates and is capturable into a hipGraph.  No
+ *   floating-point atomics: two runs agree bit for bit, on any grid.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_QFIT_SCALE 1 /* fit_mask bits */
+#define QSC_QFIT_SHIFT 2
+#define QSC_QFIT_UNCONVERGED 1 /* flags bits of qsc_qfit_finish */
+#define QSC_QFIT_UNIDENTIFIED 2
+/* Bytes of the workspace the three calls share (the state and one partial of 6 doubles per
+ * slice: 48 Pp / QSC_SLICE bytes); 0 on an invalid descriptor or rank.  Its contents carry the
+ * fit from qsc_qfit_begin to qsc_qfit_finish; one workspace serves one fit at a time. */
+QSC_API size_t qsc_qfit_workspace_bytes(const qsc_obs_desc* d, int32_t R);
+/* byte offset, in that workspace, of the int32 that is 1 while the fit is active (neither
+ * converged nor out of steps) after the last qsc_qfit_iterate: a caller may read it back now and
+ * then and stop iterating at 0 */
+QSC_API int64_t qsc_qfit_active_offset(void);
+/* S in position order [Pp][RP] (RP = qsc_rank_pad(R)), C [R][K]; kind as qsc_sinfo; fit_mask a
+ * non-empty union of QSC_QFIT_SCALE and QSC_QFIT_SHIFT.  QSC_EINVAL for m->loss ==
+ * QSC_LOSS_SQUARED, an empty or unknown fit_mask, a negative prior or mu0, tol <= 0,
+ * max_steps < 1, an unknown kind, a layout / model mismatch (qsc_sinfo's checks) or a workspace
+ * smaller than qsc_qfit_workspace_bytes; QSC_EUNSUPPORTED by qsc_sinfo's LDS rule. */
+QSC_API int qsc_qfit_begin(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                           const int64_t* s_off, const qsc_model* m, int32_t R, const float* S,
+                           const float* C, int32_t kind, int32_t fit_mask, double prior_scale,
+                           double prior_shift, double tau0, double beta0, float mu0, float tol,
+                           int32_t max_steps, void* ws, size_t ws_bytes, void* stream);
+/* (the same lists, model, R, S, C and kind as the qsc_qfit_begin of this workspace) */
+QSC_API int qsc_qfit_iterate(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                             const int64_t* s_off, const qsc_model* m, int32_t R, const float* S,
+                             const float* C, int32_t kind, void* ws, size_t ws_bytes,
+                             void* stream);
+/* All outputs are device memory.  theta_out[2] = the accepted (tau, beta);  f_out[2] = F there
+ * and F at the start, the prior terms included;  cov_out[3] (nullable) = (tt, tb, bb) of the
+ * inverse of the accepted H + diag(prior) over the fitted parameters (0 in the row and column of
+ * one that is not fitted), +inf on a pivot that is not positive, never NaN;  gh_out[5] (nullable)
+ * = the accepted g (2) and H (3: tt, tb, bb), without the prior;  *steps (nullable) = the trial
+ * evaluations used (<= max_steps; the evaluation at the start is not counted);  *flags =
+ * QSC_QFIT_UNCONVERGED | QSC_QFIT_UNIDENTIFIED as they apply (unidentified: at every step a
+ * pivot p of the fitted rows of H + diag(prior) + mu I had p <= mu -- all terms saturated and
+ * no prior, say; such a fit returns the start). */
+QSC_API int qsc_qfit_finish(const qsc_obs_desc* d, const qsc_model* m, int32_t R,
+                            double* theta_out, double* f_out, double* cov_out, double* gh_out,
+                            int32_t* steps, int32_t* flags, void* ws, size_t ws_bytes,
+                            void* stream);
+/* Elementwise terms of one entry at the map value t = T[i] and code Y[i] (the device functions of
+ * the walk, as qsc_entry_info exposes qsc_sinfo's): out[6][n] (fp64) = f, g_tau, g_beta, H_tt,
+ * H_tb, H_bb at (tau, beta); f in fp64 from the fp32 t (+inf for t + offset <= 0 in the log
+ * model), g and H the fp32 values.  Y outside [0, nbins) is clamped as qsc_prob_probit clamps it. */
+QSC_API int qsc_entry_calib(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
+                            double tau, double beta, int32_t kind, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

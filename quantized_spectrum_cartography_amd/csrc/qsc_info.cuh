@@ -186,6 +186,135 @@ __device__ __forceinline__ double entry_nll(double t, float2 e, const Link& c, d
   return -log(fmax(P, (double)FLT_MIN));
 }
 
+// ---- the model's own parameters (qsc_qfit.hip): theta = (tau, beta), a -> a e^tau, every
+// interior edge -> edge + beta ----
+// The link at the trial scale: a = fp32(a0 e^tau), a0 the fp64 divisor of the packed model
+// (probit sigma0 * 1.414213, logit s0) -- what make_link gives for sigma0 e^tau.
+__host__ __device__ __forceinline__ Link calib_link(const Link& base, bool logit, double a0,
+                                                    double tau) {
+  Link l = base;
+  l.a = (float)(a0 * exp(tau));
+  l.inv_a = 1.0f / l.a;
+  l.k1 = logit ? 1.0f / l.a : (float)(1.0 / ((double)l.a * 1.7724538509055160273));
+  return l;
+}
+
+// Is the lower / upper edge of bin b shifted by beta?  The two clamp edges of the linear model
+// (make_edges' -1e5, +1e5) are not; an infinite edge stays infinite under the addition.
+__host__ __device__ __forceinline__ bool calib_lo_shifted(int b, bool log_model) {
+  return log_model || b != 0;
+}
+__host__ __device__ __forceinline__ bool calib_hi_shifted(int b, int nbins, bool log_model) {
+  return log_model || b != nbins - 1;
+}
+// bin b's edges at beta: fp32(edge + beta), the sum in fp64
+__host__ __device__ __forceinline__ float2 calib_edges(float2 e, int b, int nbins, bool log_model,
+                                                       double beta) {
+  float2 r = e;
+  if (calib_lo_shifted(b, log_model)) r.x = (float)((double)e.x + beta);
+  if (calib_hi_shifted(b, nbins, log_model)) r.y = (float)((double)e.y + beta);
+  return r;
+}
+
+// One edge at z = (edge - x) / a, in z-units: psi = F', z psi, psi', z psi' and z^2 psi'.  A
+// saturated or infinite edge gives exactly 0 for all five (no product meets an infinity).
+//   probit: psi = exp(-z^2) / sqrt(pi), psi' = -2 z psi;   logit: psi = F (1 - F), psi' = psi (1 - 2F)
+template <bool LOGIT>
+__host__ __device__ __forceinline__ void calib_edge_terms(float z, float& A, float& B, float& D,
+                                                          float& zD, float& zzD) {
+  const bool s = !(fabsf(z) < (LOGIT ? kSatLogit : kSatProbit));
+  const float zs = s ? 0.0f : z;
+  if (LOGIT) {
+    const float E = s ? 0.0f : expf(-fabsf(zs));
+    const float r = 1.0f / (1.0f + E);
+    A = E * r * r;
+    D = A * ((zs < 0.0f ? 1.0f : -1.0f) * (1.0f - E) * r);
+  } else {
+    A = s ? 0.0f : exp_neg_sq(zs) * 0.56418958354775628695f;
+    D = -2.0f * (zs * A);
+  }
+  B = zs * A;
+  zD = zs * D;
+  zzD = zs * zD;
+}
+
+// One bin (lo, hi), already shifted, at x: P (bin_terms' value, the same operations), its first
+// derivatives P1 = (P_tau, P_beta) and second P2 = (P_tt, P_tb, P_bb), from du/dtau = -u,
+// du/dbeta = 1/a for a shifted edge and 0 for an unshifted one:
+//   P_tau = -(u psi(u) - w psi(w))                 P_beta = (psi(u) - psi(w)) / a
+//   P_tt  = (u psi + u^2 psi')(u) - (...)(w)       P_tb   = -((psi + u psi')(u) - (...)(w)) / a
+//   P_bb  = (psi'(u) - psi'(w)) / a^2
+template <bool LOGIT>
+__host__ __device__ __forceinline__ void bin_calib(float x, float lo, float hi, bool slo, bool shi,
+                                                   const Link& c, float& P, float (&P1)[2],
+                                                   float (&P2)[3]) {
+  float Px, Pxx;
+  bin_terms<LOGIT>(x, lo, hi, c, P, Px, Pxx);
+  const float u = div_link(hi - x, c), w = div_link(lo - x, c);
+  float Au, Bu, Du, zDu, zzDu, Aw, Bw, Dw, zDw, zzDw;
+  calib_edge_terms<LOGIT>(u, Au, Bu, Du, zDu, zzDu);
+  calib_edge_terms<LOGIT>(w, Aw, Bw, Dw, zDw, zzDw);
+  const float hu = shi ? 1.0f : 0.0f, hw = slo ? 1.0f : 0.0f;
+  P1[0] = -(Bu - Bw);
+  P1[1] = (hu * Au - hw * Aw) * c.inv_a;
+  P2[0] = (Bu + zzDu) - (Bw + zzDw);
+  P2[1] = -(hu * (Au + zDu) - hw * (Aw + zDw)) * c.inv_a;
+  P2[2] = (hu * Du - hw * Dw) * (c.inv_a * c.inv_a);
+}
+
+// One entry's fp32 f = -log max(P, FLT_MIN), g = (f_tau, f_beta) and H = (f_tt, f_tb, f_bb) at
+// the map value t, on the shifted edge table; `use` is false for what adds 0 to g and H.
+//   g_i = -P_i / P;  observed H_ij = P_i P_j / P^2 - P_ij / P at the entry's code;
+//   expected H_ij = sum_b P_i,b P_j,b / P_b over all bins, bins with P_b == 0 dropped (PSD)
+template <bool LOGIT, bool LOG, int KIND>
+__host__ __device__ __forceinline__ void entry_calib(float t, int code,
+                                                     const float2* __restrict__ edges,
+                                                     const Link& c, float& fe, float (&g)[2],
+                                                     float (&H)[3], bool& use, bool& neg) {
+  float x = t;
+  neg = false;
+  if (LOG) {
+    const float tp = t + c.offset;
+    neg = !(tp > 0.0f);
+    x = logf(tp);
+  }
+  const float2 e = edges[code];
+  float P, P1[2], P2[3];
+  bin_calib<LOGIT>(x, e.x, e.y, calib_lo_shifted(code, LOG), calib_hi_shifted(code, c.nbins, LOG),
+                   c, P, P1, P2);
+  // (true divisions: with a denormal P the reciprocal is +inf and 0 * inf a NaN, 0 / P is 0)
+  fe = -logf(fmaxf(P, FLT_MIN));
+  g[0] = -P1[0] / P;
+  g[1] = -P1[1] / P;
+  if (KIND == INFO_OBSERVED) {
+    H[0] = __builtin_fmaf(g[0], g[0], -P2[0] / P);
+    H[1] = __builtin_fmaf(g[0], g[1], -P2[1] / P);
+    H[2] = __builtin_fmaf(g[1], g[1], -P2[2] / P);
+  } else {
+    H[0] = H[1] = H[2] = 0.0f;
+    for (int b = 0; b < c.nbins; ++b) {
+      const float2 eb = edges[b];
+      float Pb, Q1[2], Q2[3];
+      bin_calib<LOGIT>(x, eb.x, eb.y, calib_lo_shifted(b, LOG), calib_hi_shifted(b, c.nbins, LOG),
+                       c, Pb, Q1, Q2);
+      const float qt = Q1[0] / Pb, qb = Q1[1] / Pb;
+      const bool on = Pb > 0.0f;
+      H[0] += on ? Q1[0] * qt : 0.0f;
+      H[1] += on ? Q1[1] * qt : 0.0f;
+      H[2] += on ? Q1[1] * qb : 0.0f;
+    }
+  }
+  use = (P > 0.0f) && !neg;
+}
+
+// ... and its f in fp64 by QSC_ENTRY_ACCUMULATE's rule: entry_nll at the fp64 t, but for the
+// fp32 P == 0 (FLT_MIN's term) and t + offset <= 0 (the caller makes the sum +inf)
+template <bool LOGIT, bool LOG>
+__device__ __forceinline__ double entry_calib_nll(float fe, bool neg, double t, float2 e,
+                                                  const Link& c, double inv_a) {
+  return (fe == -logf(FLT_MIN) || neg) ? (double)fe : entry_nll<LOGIT, LOG>(t, e, c, inv_a);
+}
+
 // upper-triangle index of (i, j), i <= j, of an N x N symmetric block
 template <int N>
 __host__ __device__ constexpr int tri(int i, int j) {

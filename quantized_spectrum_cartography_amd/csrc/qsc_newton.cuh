@@ -103,6 +103,37 @@ inline bool newton_args_ok(int kind, float ridge, float mu0, float tol, int step
          tol > 0.0f && steps >= 1;
 }
 
+// QSC_CHOL_SOLVE's rules for a 2 x 2 system in fp64 (qsc_qfit.hip): Cholesky of the damped
+// a = (a00, a01, a11) with a held row the identity, then delta from rhs.  ok: every pivot of a free
+// row was positive (a failed pivot, also of a NaN block, is replaced by 1); idn: every one
+// exceeded mu.
+__device__ __forceinline__ void chol2_solve_f64(const double (&a)[3], const bool (&free_)[2],
+                                                double mu, const double (&rhs)[2],
+                                                double (&delta)[2], bool& ok, bool& idn) {
+  ok = true;
+  idn = true;
+  double p0 = a[0];
+  if (free_[0]) {
+    idn = idn && (p0 > mu);
+    if (!(p0 > 0.0)) {
+      ok = false;
+      p0 = 1.0;
+    }
+  }
+  const double l10 = a[1] / p0;  // (L[1][0] / L[0][0]: the LDL^T form of the same pivots)
+  double p1 = a[2] - l10 * a[1];
+  if (free_[1]) {
+    idn = idn && (p1 > mu);
+    if (!(p1 > 0.0)) {
+      ok = false;
+      p1 = 1.0;
+    }
+  }
+  const double y1 = rhs[1] - l10 * rhs[0];
+  delta[1] = y1 / p1;
+  delta[0] = rhs[0] / p0 - l10 * delta[1];
+}
+
 }  // namespace
 
 // ---- rows of N floats (N a multiple of 4) as 16-byte vectors ----

@@ -134,6 +134,7 @@ class Observations:
             schedule = os.environ.get("QSC_SCHEDULE", "1") != "0"
         self.schedule = bool(schedule)
         self.K, self.I, self.J, self.P = K, I, J, P
+        self.R_hint = int(R_hint)
         PT = int(tile or default_tile(P, R_hint, K))
         if PT < 64 or PT % 64:
             raise ValueError("tile must be a positive multiple of 64")
@@ -316,6 +317,42 @@ class Observations:
             _lib.call("qsc_obs_schedule", desc, _lib.ptr(self.s_width), _lib.ptr(self.s_off),
                       _lib.ptr(self.c_width), _lib.ptr(self.c_off), _lib.ptr(s_entries),
                       _lib.ptr(c_entries), _lib.ptr(ws), ws.numel(), _lib.stream())
+
+    def with_model(self, noise_std=None, bin_boundaries=None):
+        """The same packed observations under another observation model: a new Observations that
+        shares the packed arrays, perm and tile and carries a new qsc_model with `noise_std` (for
+        loss="logit" the logistic scale) and / or `bin_boundaries` (None: unchanged) -- what
+        qmc.fit_noise's result is handed on with.  Nothing but the model is rebuilt: the codes do
+        not depend on it.  The row format is re-evaluated for the new model (signed rows need
+        the saturating one-bit likelihood); where it changes, the new object gets entry arrays of
+        its own, filled by the packing's own fill.  This object is left untouched.
+        Raises ValueError when the number of bins changes or noise_std is not positive."""
+        import copy
+        b = self.bin_boundaries if bin_boundaries is None else bin_boundaries
+        if isinstance(b, torch.Tensor):
+            b = b.detach().to("cpu", torch.float64).tolist()
+        b = [float(x) for x in b]
+        if len(b) != len(self.bin_boundaries):
+            raise ValueError("with_model keeps the codes: the number of bins cannot change "
+                             "(%d boundaries, got %d)" % (len(self.bin_boundaries), len(b)))
+        sigma = self.noise_std if noise_std is None else float(noise_std)
+        if not sigma > 0.0:
+            raise ValueError("noise_std must be > 0, got %r" % (noise_std,))
+        new = copy.copy(self)
+        new.model = _lib.make_model(b, sigma, self.offset if self.log_model else 0.0,
+                                    self.log_model, loss=self.loss)
+        new.noise_std, new.bin_boundaries = sigma, b
+        new.desc = _lib.QscObsDesc()
+        ctypes_copy(new.desc, self.desc)
+        R_hint = getattr(self, "R_hint", None)
+        if R_hint is not None:
+            rowfmt = 1 if new.signed_rows_ok(R_hint) else 0
+            if rowfmt != self.desc.rowfmt:
+                new.s_entries = torch.empty_like(self.s_entries)
+                new.c_entries = torch.empty_like(self.c_entries)
+                new._engines, new._code_field = 0, None
+                new._fill(rowfmt, new.desc, new.s_entries, new.c_entries)
+        return new
 
     def signed_rows_ok(self, R):
         if os.environ.get("QSC_SIGNED_ROWS", "1") == "0":  # A/B switch (tuning runs)

@@ -43,6 +43,8 @@ class SolveResult:
     polish_c: Optional["FitCResult"] = None  # solve(polish_c=n): the fit_C run on C (without C)
     # solve(polish_smooth=n): the fit_S_smooth run on S (without S)
     polish_smooth: Optional["FitSSmoothResult"] = None
+    # solve(calibrate=n): the qmc.calibrate run on S, C (without them; .obs is the calibrated one)
+    calibration: Optional["CalibrateResult"] = None
 
 
 @dataclass
@@ -373,6 +375,252 @@ def _polish(res, obs, n, lambda_s, project_s):
     res.S, r.S = r.S, None
     res.polish = r
     return res
+
+
+@dataclass
+class FitNoiseResult:
+    noise_std: float                    # sigma0 e^tau (for loss="logit" the logistic scale)
+    shift: float                        # beta, the common shift of the interior edges
+    bin_boundaries: List[float]         # the shifted list (Observations.with_model takes it)
+    nll: float                          # -sum log P at the result, without the prior terms
+    nll_start: float                    # ... at the start
+    std_log_scale: Optional[float]      # sqrt(cov[tau, tau]); None where the scale is not fitted
+    std_shift: Optional[float]          # sqrt(cov[beta, beta]); None where the shift is not fitted
+    corr: Optional[float]               # their correlation; None unless both are fitted
+    steps: int                          # trial evaluations used
+    converged: bool
+    unidentified: bool                  # H + prior never had positive pivots on the fitted set
+
+
+FIT_PARAMS = {"scale": 1, "shift": 2}  # QSC_QFIT_SCALE, QSC_QFIT_SHIFT
+
+
+def check_fit_noise(loss, fit, kind, prior, start, max_steps, tol, mu0):
+    """Validate the fit_noise arguments (before anything touches a device); the fit mask."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: fit_noise has nothing to fit')
+    fit = (fit,) if isinstance(fit, str) else tuple(fit)
+    if not fit or any(p not in FIT_PARAMS for p in fit):
+        raise ValueError("fit must name one or both of %s, got %r" % (sorted(FIT_PARAMS), fit))
+    if kind not in INFO_KINDS:
+        raise ValueError("fit_noise kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    for name, pair in (("prior", prior), ("start", start)):
+        try:
+            ok = len(pair) == 2 and all(math.isfinite(float(x)) for x in pair)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("%s must be two finite numbers (scale, shift), got %r" % (name, pair))
+    if any(float(x) < 0.0 for x in prior):
+        raise ValueError("the fit_noise prior weights must be >= 0, got %r" % (prior,))
+    if not float(mu0) >= 0.0:
+        raise ValueError("mu0 must be >= 0, got %r" % (mu0,))
+    if not float(tol) > 0.0:
+        raise ValueError("tol must be > 0, got %r" % (tol,))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1, got %r" % (max_steps,))
+    mask = 0
+    for p in fit:
+        mask |= FIT_PARAMS[p]
+    return mask
+
+
+def shifted_boundaries(bin_boundaries, shift, log_model):
+    """The boundary list with every interior edge (linear model: all but the first and last, which
+    the likelihood clamps) or every finite edge (log model) moved by `shift`: the edges qsc_qfit
+    evaluates, fp64 sums of the fp32 boundaries."""
+    b = torch.as_tensor(bin_boundaries, dtype=torch.float32).double()
+    moved = torch.isfinite(b) if log_model else torch.ones_like(b, dtype=torch.bool)
+    if not log_model:
+        moved[0] = moved[-1] = False
+    return torch.where(moved, b + float(shift), b).tolist()
+
+
+def _fit_noise_pos(obs, S_pos, C, R, kind, mask, prior, start, max_steps, tol, mu0, sync_every=4,
+                   iterate=True):
+    """qsc_qfit_begin / _iterate / _finish on a position-order S (Pp, RP) and a device C (R, K):
+    device tensors theta (2,), f (2,: F at the result and at the start, priors included),
+    cov (3,), gh (5,: g, H), all fp64, and info (2,) int32: steps, flags.  With sync_every = 0
+    nothing is read back (the sequence can be captured into a hipGraph)."""
+    desc, s_entries, _ = obs.layout(R)
+    dev = S_pos.device
+    out = torch.empty(12, dtype=torch.float64, device=dev)
+    theta, f, cov, gh = out[0:2], out[2:4], out[4:7], out[7:12]
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_qfit_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    lists = (desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off), obs.model, R,
+             _lib.ptr(S_pos), _lib.ptr(C), INFO_KINDS[kind])
+    _lib.call("qsc_qfit_begin", *lists, int(mask), float(prior[0]), float(prior[1]),
+              float(start[0]), float(start[1]), float(mu0), float(tol), int(max_steps),
+              _lib.ptr(ws), nws, _lib.stream())
+    o = int(_lib.lib().qsc_qfit_active_offset())
+    active = ws[o:o + 4].view(torch.int32)
+    for i in range(1, int(max_steps) + 1 if iterate else 0):
+        _lib.call("qsc_qfit_iterate", *lists, _lib.ptr(ws), nws, _lib.stream())
+        if sync_every and i % int(sync_every) == 0 and int(active.item()) == 0:
+            break
+    _lib.call("qsc_qfit_finish", desc, obs.model, R, _lib.ptr(theta), _lib.ptr(f), _lib.ptr(cov),
+              _lib.ptr(gh), _lib.ptr(info[0:1]), _lib.ptr(info[1:2]), _lib.ptr(ws), nws,
+              _lib.stream())
+    return theta, f, cov, gh, info
+
+
+def fit_noise(obs, S, C, fit=("scale", "shift"), kind="expected", prior=(0.0, 0.0),
+              start=(0.0, 0.0), max_steps=30, tol=1e-6, mu0=1e-3, sync_every=4):
+    """Calibrate the quantiser from the readings themselves: the noise scale and a common shift
+    of the levels, for known S and C -- the one block of the likelihood's parameters the other
+    fits take as given.
+
+    Two parameters: sigma = obs.noise_std * exp(tau) (for loss="logit" the logistic scale) and a
+    shift beta added to every interior edge of obs.bin_boundaries (the two outer edges of the
+    linear model, which the likelihood clamps, stay; under the log model every finite edge moves,
+    a common gain).  With the map T_hat = S, C fixed they minimise
+      F(tau, beta) = -sum log P(Y | T_hat; sigma, edges + beta)
+                     + prior[0] / 2 tau^2 + prior[1] / 2 beta^2
+    by damped Newton steps on a 2 x 2 system: a HIP walk over the packed S-format lists
+    (qsc_qfit.hip, include/qsc.h has the derivatives and the iteration) sums F, its gradient and
+    curvature at a trial point in a fixed order, one workgroup accepts the trial when F does not
+    increase (else raises the damping mu), solves and proposes the next, until
+    |delta|_inf <= tol (1 + |theta|_inf) or max_steps.  The whole fit is stream-ordered; every
+    sync_every steps one flag is read back to stop early (0: never; the result is the same bits).
+    obs: the Observations; S (R,1,I,J) or (R,P) and C (R,K) from a solve or the other fits.
+    fit: ("scale", "shift"), ("scale",) or ("shift",): the other parameter stays at `start`.
+    kind "expected" (Fisher scoring, the default for both models: positive semidefinite) or
+    "observed" (Newton).  prior: the weights of the quadratic priors on (tau, beta); start: where
+    the iteration begins, (0, 0) being obs's own model.
+    Returns FitNoiseResult(noise_std, shift, bin_boundaries (the shifted list), nll, nll_start
+    (both without the prior terms), std_log_scale, std_shift, corr, steps, converged,
+    unidentified); hand the model on with obs.with_model(r.noise_std, r.bin_boundaries).
+    The standard errors come from the inverse of the accepted curvature plus the prior and are
+    conditional on S and C: as qmc.confidence treats C as known, they leave out the uncertainty
+    of the map itself and are lower bounds on the joint one; they are +inf where the curvature is
+    not positive definite.  unidentified: the data do not determine the fitted parameters (every
+    term saturated and no prior, say); the result is then `start`.
+    Raises ValueError for loss="squared", an empty or unknown `fit`, an unknown kind, negative
+    prior weights or mu0, tol <= 0 or max_steps < 1, before any GPU call."""
+    mask = check_fit_noise(getattr(obs, "loss", None), fit, kind, prior, start, max_steps, tol,
+                           mu0)
+    R = S.shape[0]
+    S_pos = obs.to_positions(S.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    theta, f, cov, _, info = _fit_noise_pos(obs, S_pos, Cd, R, kind, mask, prior, start,
+                                            max_steps, tol, mu0, sync_every)
+    (tau, beta), (F, F0), (ctt, ctb, cbb) = theta.tolist(), f.tolist(), cov.tolist()
+    steps, flags = info.tolist()
+    pen = lambda t, b: 0.5 * float(prior[0]) * t * t + 0.5 * float(prior[1]) * b * b
+    has_s, has_b = bool(mask & 1), bool(mask & 2)
+    corr = None
+    if has_s and has_b:
+        corr = ctb / math.sqrt(ctt * cbb) if math.isfinite(ctt) and math.isfinite(cbb) else 0.0
+    return FitNoiseResult(
+        noise_std=obs.noise_std * math.exp(tau), shift=beta,
+        bin_boundaries=shifted_boundaries(obs.bin_boundaries, beta, obs.log_model),
+        nll=F - pen(tau, beta), nll_start=F0 - pen(float(start[0]), float(start[1])),
+        std_log_scale=math.sqrt(ctt) if has_s else None,
+        std_shift=math.sqrt(cbb) if has_b else None, corr=corr, steps=steps,
+        converged=not flags & 1, unidentified=bool(flags & 2))
+
+
+def model_nll(obs, S, C):
+    """-sum log P(Y | T_hat(S, C)) over the packed entries under obs's own model: the walk of
+    fit_noise at its start (qsc_qfit_begin, settled by qsc_qfit_finish with no step between),
+    fp64 sums in a fixed order."""
+    check_fit_noise(getattr(obs, "loss", None), ("scale",), "expected", (0.0, 0.0), (0.0, 0.0), 1,
+                    1e-6, 0.0)
+    R = S.shape[0]
+    S_pos = obs.to_positions(S.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    # (the observed kind: f is the same and its walk does not loop over the bins)
+    _, f, _, _, _ = _fit_noise_pos(obs, S_pos, Cd, R, "observed", 1, (0.0, 0.0), (0.0, 0.0), 1,
+                                   1e-6, 0.0, iterate=False)
+    return float(f[1])
+
+
+@dataclass
+class CalibrateResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J) (None in SolveResult.calibration)
+    C: Optional[torch.Tensor]           # (R, K) (None in SolveResult.calibration)
+    obs: Observations                   # the observations under the calibrated model
+    noise_std: float
+    shift: float
+    # per round the objective NLL + ridges after each block: (fit_noise, fit_C, fit_S)
+    objective: List[tuple] = field(default_factory=list)
+    fits: List[FitNoiseResult] = field(default_factory=list)
+
+
+def check_calibrate(rounds, loss, ridge_s, ridge_c):
+    """Validate the calibrate arguments (before anything touches a device); the round count."""
+    n = int(rounds)
+    if n < 1:
+        raise ValueError("rounds must be >= 1, got %r" % (rounds,))
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: there is nothing to calibrate')
+    if not float(ridge_s) >= 0.0 or not float(ridge_c) >= 0.0:
+        raise ValueError("the calibrate ridges must be >= 0, got %r, %r" % (ridge_s, ridge_c))
+    return n
+
+
+def calibrate(obs, S, C, rounds=2, ridge_s=0.0, ridge_c=0.0, fit=("scale", "shift"),
+              max_steps=30, project_s=None):
+    """Joint calibration by block-coordinate descent on NLL + ridge_s / 2 |S|^2 + ridge_c / 2 |C|^2
+    over (noise scale and shift), C and S.  Per round: fit_noise at the current S, C; the model is
+    handed on with Observations.with_model; fit_C at the current S; fit_S at the new C -- each a
+    conditional minimisation started from the current point, so the objective does not increase
+    from block to block.  Thin Python over the three fits; every argument is theirs.
+    The scale of the map and the noise scale are only jointly determined through the edges: with
+    a single threshold at 0 (or none) a common factor of T_hat and sigma leaves the likelihood
+    unchanged, and the ridges alone then pick the scale.
+    Returns CalibrateResult(S, C, obs (under the calibrated model; the packed arrays are shared
+    with the argument), noise_std, shift (the total, relative to the argument's boundaries),
+    objective (per round the three values after fit_noise, fit_C, fit_S), fits)."""
+    n = check_calibrate(rounds, getattr(obs, "loss", None), ridge_s, ridge_c)
+    check_fit_noise(obs.loss, fit, "expected", (0.0, 0.0), (0.0, 0.0), max_steps, 1e-6, 1e-3)
+    R = S.shape[0]
+    S = _dev(S.detach().to(torch.float32)).reshape(R, 1, obs.I, obs.J)
+    C = _dev(C.detach().to(torch.float32)).reshape(R, obs.K)
+    pen = lambda: (0.5 * float(ridge_s) * float((S.double() ** 2).sum())
+                   + 0.5 * float(ridge_c) * float((C.double() ** 2).sum()))
+    out = CalibrateResult(S=None, C=None, obs=obs, noise_std=obs.noise_std, shift=0.0)
+    for _ in range(n):
+        q = fit_noise(obs, S, C, fit=fit, max_steps=max_steps)
+        obs = obs.with_model(q.noise_std, q.bin_boundaries)
+        out.shift += q.shift
+        o1 = q.nll + pen()
+        c = fit_C(obs, S, C_init=C, ridge=ridge_c, max_steps=max_steps)
+        C = c.C
+        o2 = c.nll + pen()
+        s = fit_S(obs, C, S_init=S, ridge=ridge_s, max_steps=max_steps, project=project_s)
+        S = s.S
+        # (fit_S reports every pixel's f rounded to fp32; the walk of fit_noise sums the same
+        # terms in fp64, so the three values of a round compare to summation order)
+        out.objective.append((o1, o2, model_nll(obs, S, C) + pen()))
+        out.fits.append(q)
+    out.S, out.C, out.obs, out.noise_std = S, C, obs, obs.noise_std
+    return out
+
+
+def check_calibrate_solve(calibrate_, generator, loss):
+    """Validate solve(calibrate=...) (before anything touches a device); the round count."""
+    n = int(calibrate_)
+    if n < 0:
+        raise ValueError("calibrate must be >= 0, got %r" % (calibrate_,))
+    if n > 0:
+        if generator is not None:
+            raise ValueError("calibrate applies to free S only: with a generator S is not a "
+                             "free parameter")
+        if loss == "squared":
+            raise ValueError('calibrate needs a likelihood: loss="squared" has none')
+    return n
+
+
+def _calibrate_solve(res, obs, n, lambda_s, lambda_c, project_s):
+    """solve(calibrate=n): S, C <- qmc.calibrate from the returned S, C; -> the calibrated obs."""
+    r = calibrate(obs, res.S, res.C, rounds=n, ridge_s=default_confidence_ridge(res.S, lambda_s),
+                  ridge_c=default_confidence_ridge(res.C, lambda_c), project_s=project_s)
+    res.S, res.C, r.S, r.C = r.S, r.C, None, None
+    res.calibration = r
+    return r.obs
 
 
 @dataclass
@@ -1003,7 +1251,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           use_graph=False, obs=None, tile=None, callback=None, loss="probit", fuse=True,
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
-          confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0, obs_holdout=None):
+          confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0, obs_holdout=None,
+          calibrate=0):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -1071,6 +1320,14 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     refuses.  result.polish_smooth is the FitSSmoothResult (without S).  Raises ValueError with
     smooth = 0, with a generator and with loss="squared".  The default 0 leaves every path and
     result bit-identical.
+    calibrate=n > 0 (free S and holdout solves; not in the reference, which hard-codes sigma): after
+    the polish steps and before confidence= is attached, n rounds of qmc.calibrate (fit_noise, then
+    fit_C, then fit_S under the re-estimated noise scale and level shift) run from the returned S,
+    C with the ridges lambda_s / ||S||_F and lambda_c / ||C||_F of the polish steps; S and C are
+    replaced, the confidence is then evaluated under the calibrated model, and result.calibration
+    is the CalibrateResult (without S, C; its .obs carries the calibrated model).  Raises
+    ValueError with a generator and with loss="squared".  The default 0 leaves every path and
+    result bit-identical.
     obs= gives the packed observations (an Observations, e.g. Observations.from_readings for a
     list of sensor reports); Y and Wx may then be None, and K, I, J, the model and the loss are
     obs's.  obs_holdout= (with obs=, free S only) is a second Observations packed with obs.perm and
@@ -1100,6 +1357,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     polish_c = check_polish_c(polish_c, generator, obs.loss if obs is not None else loss)
     polish_smooth = check_polish_smooth(polish_smooth, generator,
                                         obs.loss if obs is not None else loss, smooth)
+    n_calibrate = check_calibrate_solve(calibrate, generator,
+                                        obs.loss if obs is not None else loss)
     if confidence is not None:
         check_confidence(confidence, confidence_ridge, obs.loss if obs is not None else loss)
         if generator is not None:
@@ -1147,6 +1406,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         if polish_smooth:
             _polish_smooth(res, obs, polish_smooth, lambda_s, project_s, smooth, smooth_kind,
                            smooth_delta)
+        if n_calibrate:
+            obs = _calibrate_solve(res, obs, n_calibrate, lambda_s, lambda_c, project_s)
         if confidence is not None:  # (on the fitted entries, the held-out ones excluded)
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res
@@ -1184,6 +1445,8 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         if polish_smooth:
             _polish_smooth(res, obs, polish_smooth, lambda_s, project_s, smooth, smooth_kind,
                            smooth_delta)
+        if n_calibrate:
+            obs = _calibrate_solve(res, obs, n_calibrate, lambda_s, lambda_c, project_s)
         if confidence is not None:
             _attach_confidence(res, obs, confidence, confidence_ridge, lambda_s)
         return res

@@ -115,3 +115,34 @@ def entry_information(T_hat, Y, bin_boundaries, noise_std, offset=0.0, log_model
     _lib.call("qsc_entry_info", _lib.ptr(Yd), _lib.ptr(Td), Td.numel(), m, INFO_KINDS[kind],
               _lib.ptr(H), _lib.stream())
     return H if T_hat.is_cuda else H.to(T_hat.device)
+
+
+def entry_calibration(Y, T, obs_or_model, tau=0.0, beta=0.0, kind="expected"):
+    """Elementwise terms of qmc.fit_noise at the map values T and codes Y: the per-entry
+    f = -log P, its gradient (g_tau, g_beta) and curvature (H_tt, H_tb, H_bb) in the log noise
+    scale tau and the level shift beta, at (tau, beta) -- the HIP op qsc_entry_calib (the device
+    functions of the fit's walk; formulas in include/qsc.h).
+
+    obs_or_model: an Observations (its model is used) or a qsc_model from _lib.make_model.
+    kind="observed": the second derivatives at the code Y; kind="expected": sum_b P_i,b P_j,b / P_b,
+    independent of Y and positive semidefinite.  Returns a float64 tensor (6, *T.shape) on T's
+    device: f in fp64 from the fp32 T (+inf where T + offset <= 0 under the log model), the five
+    derivatives the fp32 values the walk adds."""
+    from . import _lib
+    from ._model import _dev
+    from .qmc import INFO_KINDS
+    if kind not in INFO_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    m = getattr(obs_or_model, "model", obs_or_model)
+    if not isinstance(m, _lib.QscModel):
+        raise ValueError("obs_or_model must be an Observations or a qsc_model")
+    if m.loss == _lib.LOSSES["squared"]:
+        raise ValueError('loss="squared" is not a likelihood: it has no calibration terms')
+    Td = _dev(T.detach().to(torch.float32))
+    Yd = _dev(Y.to(torch.int64))
+    Yd, Td = torch.broadcast_tensors(Yd, Td)
+    Yd, Td = Yd.contiguous(), Td.contiguous()
+    out = torch.empty((6,) + tuple(Td.shape), dtype=torch.float64, device=Td.device)
+    _lib.call("qsc_entry_calib", _lib.ptr(Yd), _lib.ptr(Td), Td.numel(), m, float(tau),
+              float(beta), INFO_KINDS[kind], _lib.ptr(out), _lib.stream())
+    return out if T.is_cuda else out.to(T.device)
