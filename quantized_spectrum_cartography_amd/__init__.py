@@ -10,6 +10,9 @@ dip.py entry points.  Module map (reference file in parentheses):
   utils                   (qmc/utils.py)                   bin-edge / offset constants
   nlls                    (qmc/nlls.py)                    Gauss-Newton log-offset fit
   qmc                     (qmc/qmc.ipynb, qmc/qmc.py)      alternating solver
+  fits                                                     post-solve estimators (confidence,
+                                                           Newton fits, calibration), re-exported
+                                                           by qmc
   dip                     (qmc/dip.py, empty upstream)     deep-image-prior solver
   obs, fused                                               packed observations, fused passes
   gram                    (backup/algorithms/NMF_SPA.m)    R x R normal equations (MFMA),

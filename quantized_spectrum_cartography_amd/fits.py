@@ -1,0 +1,751 @@
+"""The post-solve estimators (not in the reference): confidence, the Newton fits fit_S, fit_C,
+fit_S_smooth and fit_noise, model_nll, calibrate, and the stage of solve() that runs them on its
+result (check_post_solve, post_solve).  Every public function validates its arguments before
+anything touches a device; the `_*_pos` drivers take a position-order S (Pp, RP) and device
+tensors.  qmc re-exports the names: qmc.fit_S etc. stay the user-facing spellings.
+"""
+import math
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import torch
+
+from . import _lib
+from ._model import _dev
+from .fused import check_smooth, smooth_kind as _kind_code
+from .obs import Observations
+
+INFO_KINDS = {"expected": 0, "observed": 1}  # QSC_INFO_EXPECTED, QSC_INFO_OBSERVED
+
+
+def _check_newton(name, loss, kind, ridge, mu0, tol, max_steps, kind_optional=True):
+    """Validate the arguments every Newton fit takes; `name` is the fit's, for the messages.
+    ridge=None: the fit has none.  kind=None (the fit picks the model's default) passes where
+    kind_optional."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: %s has nothing to fit' % name)
+    if not (kind is None and kind_optional) and kind not in INFO_KINDS:
+        raise ValueError("%s kind must be one of %s, got %r" % (name, sorted(INFO_KINDS), kind))
+    if ridge is not None and not float(ridge) >= 0.0:
+        raise ValueError("the %s ridge must be >= 0, got %r" % (name, ridge))
+    if not float(mu0) >= 0.0:
+        raise ValueError("mu0 must be >= 0, got %r" % (mu0,))
+    if not float(tol) > 0.0:
+        raise ValueError("tol must be > 0, got %r" % (tol,))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1, got %r" % (max_steps,))
+
+
+def _defaults(obs, kind, project):
+    """(kind, project) with None replaced by the model's default: Fisher scoring and S >= 0
+    under the log model, Newton and no projection otherwise."""
+    log_model = bool(getattr(obs, "log_model", False))
+    if kind is None:
+        kind = "expected" if log_model else "observed"
+    if project is None:
+        project = log_model
+    return kind, project
+
+
+def _start(obs, X_init, R, n):
+    """X_init, or the default start (R, n): ones under the log model, zeros otherwise."""
+    if X_init is None:
+        log_model = bool(getattr(obs, "log_model", False))
+        X_init = (torch.ones if log_model else torch.zeros)(R, n)
+    return X_init
+
+
+def _inputs(obs, S, C, R):
+    """(S_pos (Pp, RP) in position order, Cd (R, K) contiguous), fp32 on the device."""
+    S_pos = obs.to_positions(S.detach().to(torch.float32).reshape(R, -1))
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    return S_pos, Cd
+
+
+def _iterate(step, n, sync_every, active):
+    """Call step() up to n times; after every sync_every-th call evaluate active() (the one
+    device read-back) and stop where it is 0.  With sync_every = 0 active() is never called:
+    nothing is read back and the sequence can be captured into a hipGraph.  -> the calls made."""
+    for i in range(1, n + 1):
+        step()
+        if sync_every and i % int(sync_every) == 0 and int(active()) == 0:
+            return i
+    return n
+
+
+@dataclass
+class ConfidenceResult:
+    std_S: torch.Tensor                 # (R, 1, I, J), pixel order; +inf where unidentified
+    std_T: Optional[torch.Tensor]       # (K, 1, I, J) or None (map_std=False)
+    info: torch.Tensor                  # (P, R, R) information blocks J_p, pixel order
+    unidentified: int                   # pixels whose J_p + ridge I is not positive definite
+
+
+def check_confidence(kind, ridge, loss):
+    """Validate the confidence arguments (before anything touches a device)."""
+    if kind not in INFO_KINDS:
+        raise ValueError("confidence kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    if ridge is not None and not float(ridge) >= 0.0:
+        raise ValueError("the confidence ridge must be >= 0, got %r" % (ridge,))
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: it has no Fisher information')
+
+
+def _confidence_pos(obs, S_pos, C, R, kind, ridge, map_std):
+    """confidence() on a position-order S (Pp, RP) and a device C (R, K)."""
+    desc, s_entries, _ = obs.layout(R)
+    RP = obs.rank_pad(R)
+    dev = S_pos.device
+    J = torch.empty((obs.Pp, RP, RP), dtype=torch.float32, device=dev)
+    _lib.call("qsc_sinfo", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
+              obs.model, R, _lib.ptr(S_pos), _lib.ptr(C), INFO_KINDS[kind], _lib.ptr(J),
+              _lib.stream())
+    std_pos = torch.empty((obs.Pp, RP), dtype=torch.float32, device=dev)
+    std_T = torch.empty((obs.K, obs.P), dtype=torch.float32, device=dev) if map_std else None
+    nbad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("qsc_info_std", _lib.ptr(J), _lib.ptr(obs.perm), R, obs.P, obs.Pp, _lib.ptr(C),
+              obs.K, float(ridge), _lib.ptr(std_pos), _lib.ptr(std_T), _lib.ptr(nbad),
+              _lib.stream())
+    std_S = obs.to_pixels(std_pos, R).reshape(R, 1, obs.I, obs.J)
+    info = J[obs.iperm().long()][:, :R, :R].contiguous()
+    if std_T is not None:
+        std_T = std_T.reshape(obs.K, 1, obs.I, obs.J)
+    return ConfidenceResult(std_S=std_S, std_T=std_T, info=info, unidentified=int(nbad.item()))
+
+
+def confidence(obs, S, C, kind="expected", ridge=0.0, map_std=False):
+    """Laplace / Cramer-Rao confidence of the loss fields S and of the map at (S, C).
+
+    Conditional on C, the Hessian of the NLL in S is block diagonal: pixel p has the R x R block
+    J_p = sum_{k observed at p} h(k, p) c_k c_k^T, c_k = C[:, k], with h the curvature of one
+    entry's -log P in T_hat[k, p] (include/qsc.h, qsc_sinfo, has the formulas).  kind="expected"
+    takes the Fisher information of each entry (independent of the observed code, J_p >= 0: the
+    Cramer-Rao bound); kind="observed" the curvature at the observed code (the Hessian a double
+    backward of the NLL gives; under the log model it may be indefinite).  Then
+      std_S[r, p] = sqrt(((J_p + ridge I)^-1)[r, r]),
+      std_T[k, p] = sqrt(c_k^T (J_p + ridge I)^-1 c_k)   (map_std=True; delta method, for every
+                    map entry, observed or not).
+    A pixel whose J_p + ridge I is not positive definite (no observations and ridge = 0, say) is
+    unidentified: its standard deviations are +inf and it is counted in `unidentified`.
+    C is treated as known -- its R K parameters are informed by all observations, a pixel's R
+    values of S by that pixel's few -- so the C-side information and the S-C covariance are not
+    included: the figures are lower bounds on the joint uncertainty.
+    obs: the Observations the solve ran on; S (R,1,I,J) or (R,P), C (R,K).  Returns a
+    ConfidenceResult(std_S (R,1,I,J), std_T (K,1,I,J) or None, info (P,R,R), unidentified).
+    Raises ValueError for an unknown kind, ridge < 0 or obs.loss == "squared"."""
+    check_confidence(kind, ridge, getattr(obs, "loss", None))
+    R = S.shape[0]
+    S_pos, Cd = _inputs(obs, S, C, R)
+    return _confidence_pos(obs, S_pos, Cd, R, kind, ridge, map_std)
+
+
+def default_confidence_ridge(S, lambda_s):
+    """lambda_s / ||S||_F: the isotropic part of the Hessian of the solver's lambda_s ||S||_F
+    regulariser, (lambda_s / ||S||) (I - s s^T / ||S||^2) with s = vec(S); its rank-one part
+    couples all pixels and is dropped.  0 for S = 0."""
+    n = float(torch.linalg.norm(S.detach().to(torch.float32)))
+    return float(lambda_s) / n if n > 0.0 else 0.0
+
+
+@dataclass
+class FitSResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J), pixel order (None in SolveResult.polish)
+    nll: float                          # -sum log P at S over the observed entries (no ridge term)
+    steps: torch.Tensor                 # (I, J) int32: trial evaluations each pixel used
+    unconverged: int                    # pixels not converged within max_steps
+    unidentified: int                   # pixels whose J_p + ridge I never had positive pivots
+
+
+def check_fit_s(loss, ridge, kind, max_steps, tol, mu0):
+    """Validate the fit_S arguments (before anything touches a device)."""
+    _check_newton("fit_S", loss, kind, ridge, mu0, tol, max_steps)
+
+
+def _fit_s_pos(obs, S_pos, C, R, kind, ridge, max_steps, tol, mu0, project, S_out=None):
+    """qsc_sfit on a position-order S (Pp, RP) and a device C (R, K): (S_out, f (Pp,),
+    steps (Pp,) int32, counters (2,) int32: unconverged, unidentified), all on the device."""
+    desc, s_entries, _ = obs.layout(R)
+    dev = S_pos.device
+    if S_out is None:
+        S_out = torch.empty_like(S_pos)
+    f = torch.empty(obs.Pp, dtype=torch.float32, device=dev)
+    steps = torch.empty(obs.Pp, dtype=torch.int32, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_sfit_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    _lib.call("qsc_sfit", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
+              _lib.ptr(obs.perm), obs.model, R, _lib.ptr(C), _lib.ptr(S_pos), INFO_KINDS[kind],
+              float(ridge), float(mu0), float(tol), int(max_steps), 1 if project else 0,
+              _lib.ptr(S_out), _lib.ptr(f), _lib.ptr(steps), _lib.ptr(counters[0:1]),
+              _lib.ptr(counters[1:2]), _lib.ptr(ws), nws, _lib.stream())
+    return S_out, f, steps, counters
+
+
+def fit_S(obs, C, S_init=None, ridge=0.0, kind=None, max_steps=30, tol=1e-5, mu0=1e-3,
+          project=None):
+    """The loss fields S for known spectra C: per pixel, a damped Newton / Fisher-scoring fit.
+
+    Given C the likelihood separates over pixels; pixel p minimises
+      f_p(s) = sum_{k observed at p} -log P(Y[k, p] | s . c_k) + ridge / 2 |s|^2,
+    convex under the linear model (both links are log-concave).  One HIP launch (qsc_sfit,
+    include/qsc.h has the iteration) evaluates f, its gradient and the R x R curvature block of
+    every pixel from the packed lists, solves (J + (ridge + mu) I) delta = g + ridge s in
+    registers, accepts the step when f does not increase (else raises the damping mu), and
+    repeats until |delta|_inf <= tol (1 + |s|_inf) or max_steps -- a handful of steps where the
+    alternating solver's Adam S-step needs hundreds.  The point it returns is the conditional MLE
+    (MAP with the ridge) that qmc.confidence's standard deviations are defined at.
+    obs: the Observations; C (R, K) from an earlier solve, spa / gram.nnls_spectra or a
+    catalogue.  S_init (R,1,I,J) or (R,P): default zeros (linear model) or ones (log model).
+    kind "observed" (Newton; default for the linear model) or "expected" (Fisher scoring, always
+    positive semidefinite; default for the log model, whose observed Hessian may be indefinite).
+    project: keep S >= 0 (default: obs.log_model, as solve's project_s).  mu0: initial damping
+    (0: pure Newton steps while they are accepted).
+    Returns FitSResult(S (R,1,I,J), nll, steps (I,J), unconverged, unidentified): nll is the NLL
+    at S without the ridge term, summed in fp64 in a fixed order; unidentified counts pixels
+    whose J_p + ridge I never had all pivots positive (no observations and ridge = 0: such a
+    pixel keeps S_init).  Raises ValueError for loss="squared", negative ridge / mu0, tol <= 0,
+    max_steps < 1 or an unknown kind, before any GPU call."""
+    check_fit_s(getattr(obs, "loss", None), ridge, kind, max_steps, tol, mu0)
+    kind, project = _defaults(obs, kind, project)
+    R = C.shape[0]
+    S_pos, Cd = _inputs(obs, _start(obs, S_init, R, obs.P), C, R)
+    S_out, f, steps, counters = _fit_s_pos(obs, S_pos, Cd, R, kind, ridge, max_steps, tol, mu0,
+                                           project)
+    nll = float(f.double().sum() - 0.5 * float(ridge) * (S_out.double() ** 2).sum())
+    unconverged, unidentified = counters.tolist()
+    return FitSResult(S=obs.to_pixels(S_out, R).reshape(R, 1, obs.I, obs.J), nll=nll,
+                      steps=steps[obs.iperm().long()].reshape(obs.I, obs.J),
+                      unconverged=unconverged, unidentified=unidentified)
+
+
+@dataclass
+class FitCResult:
+    C: Optional[torch.Tensor]           # (R, K) (None in SolveResult.polish_c)
+    nll: float                          # -sum log P at C over the observed entries (no ridge term)
+    steps: torch.Tensor                 # (K,) int32: trial evaluations each bin used
+    unconverged: int                    # bins not converged within max_steps
+    unidentified: int                   # bins whose J_k + ridge I never had positive pivots
+    std_C: Optional[torch.Tensor] = None  # (R, K) sqrt(diag((J_k + ridge I)^-1)) (std=True)
+
+
+def check_fit_c(loss, ridge, kind, max_steps, tol, mu0):
+    """Validate the fit_C arguments (before anything touches a device)."""
+    _check_newton("fit_C", loss, kind, ridge, mu0, tol, max_steps)
+
+
+def _fit_c_pos(obs, S_pos, C_init, R, kind, ridge, max_steps, tol, mu0, project, std=False,
+               sync_every=4, C_out=None, ws=None):
+    """qsc_cfit_begin / _iterate / _finish on a position-order S (Pp, RP) and a device C_init
+    (R, K): (C_out, f (K,) fp64, steps (K,) int32, counters (2,) int32: unconverged,
+    unidentified, std_C or None), all on the device.  With sync_every = 0 nothing is read back
+    (the sequence can be captured into a hipGraph)."""
+    desc, _, c_entries = obs.layout(R)
+    dev = S_pos.device
+    K = obs.K
+    if C_out is None:
+        C_out = torch.empty((R, K), dtype=torch.float32, device=dev)
+    f = torch.empty(K, dtype=torch.float64, device=dev)
+    steps = torch.empty(K, dtype=torch.int32, device=dev)
+    std_C = torch.empty((R, K), dtype=torch.float32, device=dev) if std else None
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_cfit_workspace_bytes(desc, R))
+    if ws is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    lists = (desc, _lib.ptr(c_entries), _lib.ptr(obs.c_width), _lib.ptr(obs.c_off),
+             _lib.ptr(obs.c_kmap), obs.model, R, _lib.ptr(S_pos))
+    _lib.call("qsc_cfit_begin", *lists, _lib.ptr(C_init), INFO_KINDS[kind], float(ridge),
+              float(mu0), float(tol), int(max_steps), 1 if project else 0, _lib.ptr(ws), nws,
+              _lib.stream())
+    o = int(_lib.lib().qsc_cfit_active_offset())
+    active = ws[o:o + 4].view(torch.int32)
+    _iterate(lambda: _lib.call("qsc_cfit_iterate", *lists, INFO_KINDS[kind], _lib.ptr(ws), nws,
+                               _lib.stream()),
+             int(max_steps), sync_every, active.item)
+    _lib.call("qsc_cfit_finish", desc, obs.model, R, _lib.ptr(C_out), _lib.ptr(f), _lib.ptr(steps),
+              _lib.ptr(std_C), _lib.ptr(counters[0:1]), _lib.ptr(counters[1:2]), _lib.ptr(ws), nws,
+              _lib.stream())
+    return C_out, f, steps, counters, std_C
+
+
+def fit_C(obs, S, C_init=None, ridge=0.0, kind=None, max_steps=30, tol=1e-5, mu0=1e-3,
+          project=True, std=False, sync_every=4):
+    """The spectra C for known loss fields S: per frequency bin, a projected damped Newton /
+    Fisher-scoring fit of the quantized likelihood -- the mirror image of fit_S.
+
+    Given S the likelihood separates over bins; bin k minimises over c = C[:, k]
+      f_k(c) = sum_{p observed in bin k} -log P(Y[k, p] | S[:, p] . c) + ridge / 2 |c|^2,
+    R unknowns informed by every observed pixel of the bin.  A HIP walk over the packed
+    C-format lists (qsc_cfit.hip, include/qsc.h has the iteration) evaluates f, its gradient and
+    the R x R curvature block of every bin at a trial C; a second kernel accepts the trial when
+    f does not increase (else raises the damping mu), solves (J + (ridge + mu) I) delta =
+    g + ridge c on the entries that are not held at the bound, and proposes the next trial, until
+    |delta|_inf <= tol (1 + |c|_inf) or max_steps.  project=True (default: C >= 0 is the
+    solver's standing constraint) makes it a two-metric projected Newton method: entries at 0
+    whose gradient points outwards are held, the rest take the Newton step and are clipped.
+    obs: the Observations; S (R,1,I,J) or (R,P) from a propagation model, a survey or an earlier
+    solve.  C_init (R,K): default zeros (linear model) or ones (log model).  kind "observed"
+    (default for the linear model) or "expected" (default for the log model).  std=True also
+    returns std_C = sqrt(diag((J_k + ridge I)^-1)) at the result (the bound ignored; +inf for a
+    bin whose block is not positive definite).  sync_every: every so many steps the count of
+    active bins is read back and the loop stops at 0 (0: never; the result is the same bits).
+    Returns FitCResult(C (R,K), nll, steps (K,), unconverged, unidentified, std_C or None): nll is
+    the NLL at C without the ridge term (fp64 sums in a fixed order); unidentified counts bins
+    whose J_k + ridge I never had all pivots positive (no observations and ridge = 0: such a bin
+    keeps C_init).  Raises ValueError for loss="squared", negative ridge / mu0, tol <= 0,
+    max_steps < 1 or an unknown kind, before any GPU call."""
+    check_fit_c(getattr(obs, "loss", None), ridge, kind, max_steps, tol, mu0)
+    kind, project = _defaults(obs, kind, project)
+    R = S.shape[0]
+    S_pos, Cd = _inputs(obs, S, _start(obs, C_init, R, obs.K), R)
+    C_out, f, steps, counters, std_C = _fit_c_pos(obs, S_pos, Cd, R, kind, ridge, max_steps, tol,
+                                                  mu0, project, std=std, sync_every=sync_every)
+    nll = float(f.sum() - 0.5 * float(ridge) * (C_out.double() ** 2).sum())
+    unconverged, unidentified = counters.tolist()
+    return FitCResult(C=C_out, nll=nll, steps=steps, unconverged=unconverged,
+                      unidentified=unidentified, std_C=std_C)
+
+
+@dataclass
+class FitNoiseResult:
+    noise_std: float                    # sigma0 e^tau (for loss="logit" the logistic scale)
+    shift: float                        # beta, the common shift of the interior edges
+    bin_boundaries: List[float]         # the shifted list (Observations.with_model takes it)
+    nll: float                          # -sum log P at the result, without the prior terms
+    nll_start: float                    # ... at the start
+    std_log_scale: Optional[float]      # sqrt(cov[tau, tau]); None where the scale is not fitted
+    std_shift: Optional[float]          # sqrt(cov[beta, beta]); None where the shift is not fitted
+    corr: Optional[float]               # their correlation; None unless both are fitted
+    steps: int                          # trial evaluations used
+    converged: bool
+    unidentified: bool                  # H + prior never had positive pivots on the fitted set
+
+
+FIT_PARAMS = {"scale": 1, "shift": 2}  # QSC_QFIT_SCALE, QSC_QFIT_SHIFT
+
+
+def check_fit_noise(loss, fit, kind, prior, start, max_steps, tol, mu0):
+    """Validate the fit_noise arguments (before anything touches a device); the fit mask."""
+    _check_newton("fit_noise", loss, kind, None, mu0, tol, max_steps, kind_optional=False)
+    fit = (fit,) if isinstance(fit, str) else tuple(fit)
+    if not fit or any(p not in FIT_PARAMS for p in fit):
+        raise ValueError("fit must name one or both of %s, got %r" % (sorted(FIT_PARAMS), fit))
+    for name, pair in (("prior", prior), ("start", start)):
+        try:
+            ok = len(pair) == 2 and all(math.isfinite(float(x)) for x in pair)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("%s must be two finite numbers (scale, shift), got %r" % (name, pair))
+    if any(float(x) < 0.0 for x in prior):
+        raise ValueError("the fit_noise prior weights must be >= 0, got %r" % (prior,))
+    mask = 0
+    for p in fit:
+        mask |= FIT_PARAMS[p]
+    return mask
+
+
+def shifted_boundaries(bin_boundaries, shift, log_model):
+    """The boundary list with every interior edge (linear model: all but the first and last, which
+    the likelihood clamps) or every finite edge (log model) moved by `shift`: the edges qsc_qfit
+    evaluates, fp64 sums of the fp32 boundaries."""
+    b = torch.as_tensor(bin_boundaries, dtype=torch.float32).double()
+    moved = torch.isfinite(b) if log_model else torch.ones_like(b, dtype=torch.bool)
+    if not log_model:
+        moved[0] = moved[-1] = False
+    return torch.where(moved, b + float(shift), b).tolist()
+
+
+def _fit_noise_pos(obs, S_pos, C, R, kind, mask, prior, start, max_steps, tol, mu0, sync_every=4,
+                   iterate=True):
+    """qsc_qfit_begin / _iterate / _finish on a position-order S (Pp, RP) and a device C (R, K):
+    device tensors theta (2,), f (2,: F at the result and at the start, priors included),
+    cov (3,), gh (5,: g, H), all fp64, and info (2,) int32: steps, flags.  With sync_every = 0
+    nothing is read back (the sequence can be captured into a hipGraph)."""
+    desc, s_entries, _ = obs.layout(R)
+    dev = S_pos.device
+    out = torch.empty(12, dtype=torch.float64, device=dev)
+    theta, f, cov, gh = out[0:2], out[2:4], out[4:7], out[7:12]
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_qfit_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    lists = (desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off), obs.model, R,
+             _lib.ptr(S_pos), _lib.ptr(C), INFO_KINDS[kind])
+    _lib.call("qsc_qfit_begin", *lists, int(mask), float(prior[0]), float(prior[1]),
+              float(start[0]), float(start[1]), float(mu0), float(tol), int(max_steps),
+              _lib.ptr(ws), nws, _lib.stream())
+    o = int(_lib.lib().qsc_qfit_active_offset())
+    active = ws[o:o + 4].view(torch.int32)
+    _iterate(lambda: _lib.call("qsc_qfit_iterate", *lists, _lib.ptr(ws), nws, _lib.stream()),
+             int(max_steps) if iterate else 0, sync_every, active.item)
+    _lib.call("qsc_qfit_finish", desc, obs.model, R, _lib.ptr(theta), _lib.ptr(f), _lib.ptr(cov),
+              _lib.ptr(gh), _lib.ptr(info[0:1]), _lib.ptr(info[1:2]), _lib.ptr(ws), nws,
+              _lib.stream())
+    return theta, f, cov, gh, info
+
+
+def fit_noise(obs, S, C, fit=("scale", "shift"), kind="expected", prior=(0.0, 0.0),
+              start=(0.0, 0.0), max_steps=30, tol=1e-6, mu0=1e-3, sync_every=4):
+    """Calibrate the quantiser from the readings themselves: the noise scale and a common shift
+    of the levels, for known S and C -- the one block of the likelihood's parameters the other
+    fits take as given.
+
+    Two parameters: sigma = obs.noise_std * exp(tau) (for loss="logit" the logistic scale) and a
+    shift beta added to every interior edge of obs.bin_boundaries (the two outer edges of the
+    linear model, which the likelihood clamps, stay; under the log model every finite edge moves,
+    a common gain).  With the map T_hat = S, C fixed they minimise
+      F(tau, beta) = -sum log P(Y | T_hat; sigma, edges + beta)
+                     + prior[0] / 2 tau^2 + prior[1] / 2 beta^2
+    by damped Newton steps on a 2 x 2 system: a HIP walk over the packed S-format lists
+    (qsc_qfit.hip, include/qsc.h has the derivatives and the iteration) sums F, its gradient and
+    curvature at a trial point in a fixed order, one workgroup accepts the trial when F does not
+    increase (else raises the damping mu), solves and proposes the next, until
+    |delta|_inf <= tol (1 + |theta|_inf) or max_steps.  The whole fit is stream-ordered; every
+    sync_every steps one flag is read back to stop early (0: never; the result is the same bits).
+    obs: the Observations; S (R,1,I,J) or (R,P) and C (R,K) from a solve or the other fits.
+    fit: ("scale", "shift"), ("scale",) or ("shift",): the other parameter stays at `start`.
+    kind "expected" (Fisher scoring, the default for both models: positive semidefinite) or
+    "observed" (Newton).  prior: the weights of the quadratic priors on (tau, beta); start: where
+    the iteration begins, (0, 0) being obs's own model.
+    Returns FitNoiseResult(noise_std, shift, bin_boundaries (the shifted list), nll, nll_start
+    (both without the prior terms), std_log_scale, std_shift, corr, steps, converged,
+    unidentified); hand the model on with obs.with_model(r.noise_std, r.bin_boundaries).
+    The standard errors come from the inverse of the accepted curvature plus the prior and are
+    conditional on S and C: as qmc.confidence treats C as known, they leave out the uncertainty
+    of the map itself and are lower bounds on the joint one; they are +inf where the curvature is
+    not positive definite.  unidentified: the data do not determine the fitted parameters (every
+    term saturated and no prior, say); the result is then `start`.
+    Raises ValueError for loss="squared", an empty or unknown `fit`, an unknown kind, negative
+    prior weights or mu0, tol <= 0 or max_steps < 1, before any GPU call."""
+    mask = check_fit_noise(getattr(obs, "loss", None), fit, kind, prior, start, max_steps, tol,
+                           mu0)
+    R = S.shape[0]
+    S_pos, Cd = _inputs(obs, S, C, R)
+    theta, f, cov, _, info = _fit_noise_pos(obs, S_pos, Cd, R, kind, mask, prior, start,
+                                            max_steps, tol, mu0, sync_every)
+    (tau, beta), (F, F0), (ctt, ctb, cbb) = theta.tolist(), f.tolist(), cov.tolist()
+    steps, flags = info.tolist()
+    pen = lambda t, b: 0.5 * float(prior[0]) * t * t + 0.5 * float(prior[1]) * b * b
+    has_s, has_b = bool(mask & 1), bool(mask & 2)
+    corr = None
+    if has_s and has_b:
+        corr = ctb / math.sqrt(ctt * cbb) if math.isfinite(ctt) and math.isfinite(cbb) else 0.0
+    return FitNoiseResult(
+        noise_std=obs.noise_std * math.exp(tau), shift=beta,
+        bin_boundaries=shifted_boundaries(obs.bin_boundaries, beta, obs.log_model),
+        nll=F - pen(tau, beta), nll_start=F0 - pen(float(start[0]), float(start[1])),
+        std_log_scale=math.sqrt(ctt) if has_s else None,
+        std_shift=math.sqrt(cbb) if has_b else None, corr=corr, steps=steps,
+        converged=not flags & 1, unidentified=bool(flags & 2))
+
+
+def model_nll(obs, S, C):
+    """-sum log P(Y | T_hat(S, C)) over the packed entries under obs's own model: the walk of
+    fit_noise at its start (qsc_qfit_begin, settled by qsc_qfit_finish with no step between),
+    fp64 sums in a fixed order."""
+    check_fit_noise(getattr(obs, "loss", None), ("scale",), "expected", (0.0, 0.0), (0.0, 0.0), 1,
+                    1e-6, 0.0)
+    R = S.shape[0]
+    S_pos, Cd = _inputs(obs, S, C, R)
+    # (the observed kind: f is the same and its walk does not loop over the bins)
+    _, f, _, _, _ = _fit_noise_pos(obs, S_pos, Cd, R, "observed", 1, (0.0, 0.0), (0.0, 0.0), 1,
+                                   1e-6, 0.0, iterate=False)
+    return float(f[1])
+
+
+@dataclass
+class CalibrateResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J) (None in SolveResult.calibration)
+    C: Optional[torch.Tensor]           # (R, K) (None in SolveResult.calibration)
+    obs: Observations                   # the observations under the calibrated model
+    noise_std: float
+    shift: float
+    # per round the objective NLL + ridges after each block: (fit_noise, fit_C, fit_S)
+    objective: List[tuple] = field(default_factory=list)
+    fits: List[FitNoiseResult] = field(default_factory=list)
+
+
+def check_calibrate(rounds, loss, ridge_s, ridge_c):
+    """Validate the calibrate arguments (before anything touches a device); the round count."""
+    n = int(rounds)
+    if n < 1:
+        raise ValueError("rounds must be >= 1, got %r" % (rounds,))
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: there is nothing to calibrate')
+    if not float(ridge_s) >= 0.0 or not float(ridge_c) >= 0.0:
+        raise ValueError("the calibrate ridges must be >= 0, got %r, %r" % (ridge_s, ridge_c))
+    return n
+
+
+def calibrate(obs, S, C, rounds=2, ridge_s=0.0, ridge_c=0.0, fit=("scale", "shift"),
+              max_steps=30, project_s=None):
+    """Joint calibration by block-coordinate descent on NLL + ridge_s / 2 |S|^2 + ridge_c / 2 |C|^2
+    over (noise scale and shift), C and S.  Per round: fit_noise at the current S, C; the model is
+    handed on with Observations.with_model; fit_C at the current S; fit_S at the new C -- each a
+    conditional minimisation started from the current point, so the objective does not increase
+    from block to block.  Thin Python over the three fits; every argument is theirs.
+    The scale of the map and the noise scale are only jointly determined through the edges: with
+    a single threshold at 0 (or none) a common factor of T_hat and sigma leaves the likelihood
+    unchanged, and the ridges alone then pick the scale.
+    Returns CalibrateResult(S, C, obs (under the calibrated model; the packed arrays are shared
+    with the argument), noise_std, shift (the total, relative to the argument's boundaries),
+    objective (per round the three values after fit_noise, fit_C, fit_S), fits)."""
+    n = check_calibrate(rounds, getattr(obs, "loss", None), ridge_s, ridge_c)
+    check_fit_noise(obs.loss, fit, "expected", (0.0, 0.0), (0.0, 0.0), max_steps, 1e-6, 1e-3)
+    R = S.shape[0]
+    S = _dev(S.detach().to(torch.float32)).reshape(R, 1, obs.I, obs.J)
+    C = _dev(C.detach().to(torch.float32)).reshape(R, obs.K)
+    pen = lambda: (0.5 * float(ridge_s) * float((S.double() ** 2).sum())
+                   + 0.5 * float(ridge_c) * float((C.double() ** 2).sum()))
+    out = CalibrateResult(S=None, C=None, obs=obs, noise_std=obs.noise_std, shift=0.0)
+    for _ in range(n):
+        q = fit_noise(obs, S, C, fit=fit, max_steps=max_steps)
+        obs = obs.with_model(q.noise_std, q.bin_boundaries)
+        out.shift += q.shift
+        o1 = q.nll + pen()
+        c = fit_C(obs, S, C_init=C, ridge=ridge_c, max_steps=max_steps)
+        C = c.C
+        o2 = c.nll + pen()
+        s = fit_S(obs, C, S_init=S, ridge=ridge_s, max_steps=max_steps, project=project_s)
+        S = s.S
+        # (fit_S reports every pixel's f rounded to fp32; the walk of fit_noise sums the same
+        # terms in fp64, so the three values of a round compare to summation order)
+        out.objective.append((o1, o2, model_nll(obs, S, C) + pen()))
+        out.fits.append(q)
+    out.S, out.C, out.obs, out.noise_std = S, C, obs, obs.noise_std
+    return out
+
+
+@dataclass
+class FitSSmoothResult:
+    S: Optional[torch.Tensor]           # (R, 1, I, J), pixel order (None in SolveResult.polish_smooth)
+    nll: float                          # -sum log P at S over the observed entries
+    penalty: float                      # R(S), unweighted (qsc_smooth_grad)
+    objective: float                    # nll + ridge / 2 |S|^2 + smooth * penalty
+    sweeps: int                         # sweeps run (a sweep: colour 0, then colour 1)
+    steps: torch.Tensor                 # (I, J) int32: trial evaluations each pixel used in all
+    moved: int                          # pixels the last sweep moved by more than tol (1 + |s|_inf)
+    unconverged: int                    # pixels of the last sweep whose last trial was not an
+                                        # accepted step within tol (stalled pixels among them)
+    unidentified: int                   # pixels of the last sweep whose J + prior + ridge never
+                                        # had positive pivots
+
+
+def check_fit_s_smooth(loss, smooth, smooth_kind, smooth_delta, ridge, kind, sweeps, inner_steps,
+                       tol, mu0):
+    """Validate the fit_S_smooth arguments (before anything touches a device); float(smooth)."""
+    if int(inner_steps) < 1:
+        raise ValueError("inner_steps must be >= 1, got %r" % (inner_steps,))
+    check_fit_s(loss, ridge, kind, inner_steps, tol, mu0)
+    smooth = check_smooth(smooth, smooth_kind, smooth_delta)
+    if not smooth > 0.0:
+        raise ValueError("fit_S_smooth needs smooth > 0, got %r: without the prior the pixels are "
+                         "independent and fit_S fits them in one launch" % (smooth,))
+    if int(sweeps) < 1:
+        raise ValueError("sweeps must be >= 1, got %r" % (sweeps,))
+    return smooth
+
+
+def _sfit_smooth_bufs(obs, R, sweeps):
+    """The device buffers of a run of visits: (f, nll, steps (zeroed), counters (sweeps, 2, 3)
+    int32 zeroed -- one (n_moved, n_unconverged, n_unidentified) triple per visit, so that no
+    launch waits for a reset -- and the workspace or None)."""
+    desc, _, _ = obs.layout(R)
+    dev = obs.device
+    f = torch.zeros(obs.Pp, dtype=torch.float32, device=dev)
+    nll = torch.zeros(obs.Pp, dtype=torch.float32, device=dev)
+    steps = torch.zeros(obs.Pp, dtype=torch.int32, device=dev)
+    counters = torch.zeros((int(sweeps), 2, 3), dtype=torch.int32, device=dev)
+    nws = int(_lib.lib().qsc_sfit_smooth_workspace_bytes(desc, R))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    return f, nll, steps, counters, ws
+
+
+def _sfit_smooth_visit(obs, S_pos, C, R, color, kind, ridge, inner_steps, tol, mu0, project,
+                       smooth_code, delta, weight, f, nll, steps, cnt, ws):
+    """qsc_sfit_smooth: one visit of one colour, in place on the position-order S_pos (Pp, RP);
+    cnt a (3,) int32 device view (n_moved, n_unconverged, n_unidentified) the call adds to."""
+    desc, s_entries, _ = obs.layout(R)
+    _lib.call("qsc_sfit_smooth", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width),
+              _lib.ptr(obs.s_off), _lib.ptr(obs.perm), _lib.ptr(obs.neighbors()), obs.I, obs.J,
+              int(color), obs.model, R, _lib.ptr(C), _lib.ptr(S_pos), INFO_KINDS[kind],
+              float(ridge), float(mu0), float(tol), int(inner_steps), 1 if project else 0,
+              smooth_code, float(delta), float(weight), _lib.ptr(f), _lib.ptr(nll),
+              _lib.ptr(steps), _lib.ptr(cnt[0:1]), _lib.ptr(cnt[1:2]), _lib.ptr(cnt[2:3]),
+              _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream())
+
+
+def _fit_s_smooth_pos(obs, S_pos, C, R, kind, ridge, sweeps, inner_steps, tol, mu0, project,
+                      smooth_kind_, smooth_delta, weight, sync_every=4):
+    """Red-black sweeps of qsc_sfit_smooth in place on S_pos: (nll (Pp,), steps (Pp,),
+    counters (sweeps, 2, 3), sweeps run).  With sync_every = 0 nothing is read back."""
+    code, delta = _kind_code(smooth_kind_, smooth_delta)
+    f, nll, steps, counters, ws = _sfit_smooth_bufs(obs, R, sweeps)
+    # (not _iterate: a sweep writes, and the read-back sums, its own row of the counters)
+    n = 0
+    for i in range(int(sweeps)):
+        for color in (0, 1):
+            _sfit_smooth_visit(obs, S_pos, C, R, color, kind, ridge, inner_steps, tol, mu0,
+                               project, code, delta, weight, f, nll, steps, counters[i, color], ws)
+        n = i + 1
+        if sync_every and n % int(sync_every) == 0 and int(counters[i, :, 0].sum().item()) == 0:
+            break
+    return nll, steps, counters, n
+
+
+def _smooth_penalty_pos(obs, S_pos, R, smooth_kind_, smooth_delta):
+    """R(S), unweighted, of a position-order S (qsc_smooth_grad with dS = NULL); synchronises."""
+    code, delta = _kind_code(smooth_kind_, smooth_delta)
+    dev = S_pos.device
+    nb = int(_lib.lib().qsc_smooth_workspace_bytes(obs.Pp))
+    if nb == 0:
+        raise _lib.QscError("the smoothness prior does not support Pp = %d" % obs.Pp)
+    ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    pen = torch.zeros(1, dtype=torch.float32, device=dev)
+    _lib.call("qsc_smooth_grad", _lib.ptr(S_pos), _lib.ptr(obs.neighbors()), R, obs.Pp, code,
+              delta, 1.0, None, _lib.ptr(pen), None, 0, _lib.ptr(ws), ws.numel(), _lib.stream())
+    return float(pen.item())
+
+
+def fit_S_smooth(obs, C, smooth, smooth_kind="quad", smooth_delta=None, S_init=None, ridge=0.0,
+                 kind=None, sweeps=20, inner_steps=2, tol=1e-5, mu0=1e-3, project=None,
+                 sync_every=4):
+    """The loss fields S for known spectra C under the smoothness prior: red-black Newton sweeps.
+
+    Minimises F(S) = NLL(S) + ridge / 2 |S|^2 + smooth * R(S), R the prior of solve(smooth=...)
+    ("quad" or "huber" with smooth_delta).  The prior couples each pixel to its 4 grid neighbours
+    only, and that graph is bipartite in the colour (i + j) & 1: with one colour held fixed the
+    pixels of the other are independent, and each takes up to inner_steps damped Newton steps of
+    fit_S's iteration on its own phi = f + smooth * (prior terms of its edges) in one HIP launch
+    (qsc_sfit_smooth, include/qsc.h).  A sweep is colour 0 then colour 1; every accepted step
+    lowers its pixel's phi, so F never increases (block coordinate descent; F is convex under the
+    linear model).  A pixel without observations is determined by its neighbours.
+    obs, C, S_init, ridge, kind, tol, mu0, project: as fit_S (the same defaults).  Every
+    sync_every sweeps the count of pixels the sweep moved by more than tol (1 + |s|_inf) is read
+    back and the fit stops at 0 (sync_every=0: never, all sweeps run; the result is the same bits
+    where none stops early).  A visit restarts the damping at mu0 and has inner_steps trials: a
+    pixel whose trials are all rejected (far in a link's tail, from S = 0 under the logit or log
+    model, say) does not move and is not counted in `moved`, so start such fits from a solver's
+    S, as polish_smooth does, or raise inner_steps.  `unconverged` counts the pixels whose last
+    trial of the last sweep was not an accepted step within tol: every stalled pixel, but also
+    the many pixels of a converged fit whose last, rounding-sized step is rejected (117 of 135
+    against a stall's 134 on the logit test input), so it is a hint, not a test of convergence.
+    Returns FitSSmoothResult(S (R,1,I,J), nll, penalty, objective, sweeps, steps (I,J), moved,
+    unconverged, unidentified): nll the fp64 sum of the per-pixel NLL in a fixed order, penalty R(S) unweighted
+    (qsc_smooth_grad), objective = nll + ridge / 2 |S|^2 + smooth * penalty, moved and
+    unidentified of the last sweep run.  Raises ValueError for smooth <= 0 (use fit_S), sweeps or
+    inner_steps < 1, an unknown smooth_kind, huber without delta > 0 and everything fit_S raises
+    for, before any GPU call."""
+    smooth = check_fit_s_smooth(getattr(obs, "loss", None), smooth, smooth_kind, smooth_delta,
+                                ridge, kind, sweeps, inner_steps, tol, mu0)
+    kind, project = _defaults(obs, kind, project)
+    R = C.shape[0]
+    S_pos, Cd = _inputs(obs, _start(obs, S_init, R, obs.P), C, R)
+    nll_pos, steps, counters, n = _fit_s_smooth_pos(obs, S_pos, Cd, R, kind, ridge, sweeps,
+                                                    inner_steps, tol, mu0, project, smooth_kind,
+                                                    smooth_delta, smooth, sync_every=sync_every)
+    pen = _smooth_penalty_pos(obs, S_pos, R, smooth_kind, smooth_delta)
+    nll = float(nll_pos.double().sum())
+    normsq = float((S_pos.double() ** 2).sum())
+    moved, unconverged, unidentified = counters[n - 1].sum(dim=0).tolist()
+    return FitSSmoothResult(S=obs.to_pixels(S_pos, R).reshape(R, 1, obs.I, obs.J), nll=nll,
+                            penalty=pen, objective=nll + 0.5 * float(ridge) * normsq + smooth * pen,
+                            sweeps=n, steps=steps[obs.iperm().long()].reshape(obs.I, obs.J),
+                            moved=int(moved), unconverged=int(unconverged),
+                            unidentified=int(unidentified))
+
+
+@dataclass
+class PostSolve:
+    """solve()'s validated post-solve options (check_post_solve): the four counts, 0 = off, and
+    the confidence kind (None = off) with its ridge (None = default_confidence_ridge)."""
+    polish_c: int = 0
+    polish_s: int = 0
+    polish_smooth: int = 0
+    calibrate: int = 0
+    confidence: Optional[str] = None
+    confidence_ridge: Optional[float] = None
+
+
+def _check_option(name, value, generator, loss):
+    """The rules every post-solve option of solve() shares: a count >= 0 and, where it is on, a
+    free S and a likelihood.  -> the count."""
+    n = int(value)
+    if n < 0:
+        raise ValueError("%s must be >= 0, got %r" % (name, value))
+    if n > 0:
+        if generator is not None:
+            raise ValueError("%s applies to free S only: with a generator S is not a free "
+                             "parameter" % name)
+        if loss == "squared":
+            raise ValueError('%s needs a likelihood: loss="squared" has none' % name)
+    return n
+
+
+def check_polish_c(polish_c, generator, loss):
+    """Validate solve(polish_c=...) (before anything touches a device); the step count.  The
+    smoothness prior is allowed: it does not involve C."""
+    return _check_option("polish_c", polish_c, generator, loss)
+
+
+def check_post_solve(generator, loss, smooth, polish_s=0, polish_c=0, polish_smooth=0, calibrate=0,
+                     confidence=None, confidence_ridge=None):
+    """Validate solve(polish_s=, polish_c=, polish_smooth=, calibrate=, confidence=,
+    confidence_ridge=) (before anything touches a device) -> PostSolve.  `smooth` is solve's
+    checked weight of the smoothness prior."""
+    n_s = _check_option("polish_s", polish_s, generator, loss)
+    if n_s and smooth > 0.0:
+        raise ValueError("polish_s fits every pixel on its own; the smoothness prior "
+                         "(smooth > 0) couples pixels")
+    n_c = check_polish_c(polish_c, generator, loss)
+    n_smooth = _check_option("polish_smooth", polish_smooth, generator, loss)
+    if n_smooth and not smooth > 0.0:
+        raise ValueError("polish_smooth fits S under the smoothness prior: it needs "
+                         "smooth > 0 (without the prior, polish_s fits every pixel on its own)")
+    n_cal = _check_option("calibrate", calibrate, generator, loss)
+    if _check_option("confidence", confidence is not None, generator, loss):
+        check_confidence(confidence, confidence_ridge, loss)
+    return PostSolve(polish_c=n_c, polish_s=n_s, polish_smooth=n_smooth, calibrate=n_cal,
+                     confidence=confidence, confidence_ridge=confidence_ridge)
+
+
+def post_solve(res, obs, opts, lambda_s, lambda_c, project_s, smooth, smooth_kind, smooth_delta):
+    """solve()'s post-solve stage on the SolveResult `res` of a free-S or holdout solve on `obs`,
+    in this order, each step started from the S, C the one before left in `res`:
+      polish_c       C <- fit_C at S, ridge lambda_c / ||C||_F; res.polish_c (without C)
+      polish_s       S <- fit_S at C, ridge lambda_s / ||S||_F; res.polish (without S)
+      polish_smooth  S <- that many sweeps of fit_S_smooth at C under the solve's prior, the
+                     ridge of polish_s; res.polish_smooth (without S)
+      calibrate      S, C <- that many rounds of calibrate with both ridges; res.calibration
+                     (without S, C); what follows runs on its .obs, the calibrated model
+      confidence     res.std_S and res.unidentified at the returned S, C, the ridge
+                     opts.confidence_ridge or lambda_s / ||S||_F
+    opts: check_post_solve's PostSolve; a step that is off is skipped.  -> res."""
+    if opts.polish_c:
+        r = fit_C(obs, res.S, C_init=res.C, ridge=default_confidence_ridge(res.C, lambda_c),
+                  max_steps=opts.polish_c, project=True)
+        res.C, r.C = r.C, None
+        res.polish_c = r
+    if opts.polish_s:
+        r = fit_S(obs, res.C, S_init=res.S, ridge=default_confidence_ridge(res.S, lambda_s),
+                  max_steps=opts.polish_s, project=project_s)
+        res.S, r.S = r.S, None
+        res.polish = r
+    if opts.polish_smooth:
+        r = fit_S_smooth(obs, res.C, smooth, smooth_kind=smooth_kind, smooth_delta=smooth_delta,
+                         S_init=res.S, ridge=default_confidence_ridge(res.S, lambda_s),
+                         sweeps=opts.polish_smooth, project=project_s)
+        res.S, r.S = r.S, None
+        res.polish_smooth = r
+    if opts.calibrate:
+        r = calibrate(obs, res.S, res.C, rounds=opts.calibrate,
+                      ridge_s=default_confidence_ridge(res.S, lambda_s),
+                      ridge_c=default_confidence_ridge(res.C, lambda_c), project_s=project_s)
+        res.S, res.C, r.S, r.C = r.S, r.C, None, None
+        res.calibration = r
+        obs = r.obs
+    if opts.confidence is not None:
+        ridge = (default_confidence_ridge(res.S, lambda_s) if opts.confidence_ridge is None
+                 else float(opts.confidence_ridge))
+        c = confidence(obs, res.S, res.C, kind=opts.confidence, ridge=ridge)
+        res.std_S, res.unidentified = c.std_S, c.unidentified
+    return res

@@ -103,7 +103,7 @@ def entry_information(T_hat, Y, bin_boundaries, noise_std, offset=0.0, log_model
     then the logistic scale).  Returns a float32 tensor shaped like T_hat on T_hat's device."""
     from . import _lib
     from ._model import _dev
-    from .qmc import check_confidence, INFO_KINDS
+    from .fits import check_confidence, INFO_KINDS
     check_confidence(kind, None, loss)
     m = _lib.make_model(bin_boundaries, noise_std, offset if log_model else 0.0, log_model,
                         loss=loss)
@@ -130,7 +130,7 @@ def entry_calibration(Y, T, obs_or_model, tau=0.0, beta=0.0, kind="expected"):
     derivatives the fp32 values the walk adds."""
     from . import _lib
     from ._model import _dev
-    from .qmc import INFO_KINDS
+    from .fits import INFO_KINDS
     if kind not in INFO_KINDS:
         raise ValueError("kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
     m = getattr(obs_or_model, "model", obs_or_model)
