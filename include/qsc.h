@@ -534,6 +534,45 @@ QSC_API int qsc_entry_info(const int64_t* Y, const float* T, int64_t n, const qs
                            int32_t kind, float* H, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Expected information gain of planned readings, per position (qsc_design.hip): where to
+ * measure next.
+ *   A plan is w[K], w_k >= 0: the number of readings planned in bin k (NULL: one of every bin).
+ *   Conditional on C the positions are independent, so the value of the plan at position q is
+ *   a figure of that position alone, and the best n distinct sites are the top n.  With J_q the
+ *   block of the readings already held (qsc_sinfo, either kind), t_kq = S[q] . c_k and h_exp the
+ *   QSC_INFO_EXPECTED curvature above (it does not depend on the code a reading will return):
+ *     A_q = sum_k w_k h_exp(t_kq) c_k c_k^T,   M0 = J_q + ridge I,   M1 = M0 + A_q
+ *     QSC_DESIGN_D:  1/2 (logdet M1 - logdet M0)            expected entropy reduction, nats
+ *     QSC_DESIGN_A:  tr(M0^-1) - tr(M1^-1)                  reduction of sum_r var(S_r)
+ *     QSC_DESIGN_V:  tr(G M0^-1) - tr(G M1^-1), G = C C^T   reduction of sum_k var(T_hat[k, q])
+ *   Rows and columns >= R are replaced by the identity (qsc_info_std's rule) and contribute 0.
+ *   A bin with w_k == 0 adds exactly 0 and is not evaluated; in the log model an entry with
+ *   t + offset <= 0 adds 0.  The factorisations are qsc_info_std's Cholesky with its pivot rule:
+ *     M0 not positive definite, M1 positive definite (an unobserved position with ridge = 0):
+ *       gain = +inf, a first look, counted into *n_first;
+ *     M1 not positive definite (or a figure that is not finite): gain = 0, counted into *n_bad;
+ *   never NaN, and never negative (a difference that rounds below 0 is written as 0).  Padding
+ *   positions (perm[q] < 0) are written as 0 and not counted.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_DESIGN_D 0
+#define QSC_DESIGN_A 1
+#define QSC_DESIGN_V 2
+/* gain[Pp] (fp32, position order) from S [Pp][RP] (position order, RP = qsc_rank_pad(R)),
+ * C [R][K], the blocks J[Pp][RP][RP] of qsc_sinfo and perm[Pp] as qsc_info_std; w[K] nullable;
+ * G[RP][RP] (C C^T, rows and columns >= R zero) is read for QSC_DESIGN_V only.  The walk is dense
+ * over k: no observation lists are needed.  Two lanes per position, each sums alternate bins in
+ * order of k; *n_first and *n_bad are device int32 the caller zeroes (integer atomics only): two
+ * calls agree bit for bit.  No workspace, no allocation, stream-ordered, capturable.
+ * QSC_EINVAL for m->loss == QSC_LOSS_SQUARED or a bad model, R outside [1, QSC_MAX_R], K or P < 1,
+ * Pp < P or no multiple of QSC_SLICE, ridge < 0 or NaN, an unknown criterion, or G == NULL with
+ * QSC_DESIGN_V; QSC_EUNSUPPORTED when C^T, the bin edges and w exceed the 160 KiB of LDS
+ * (qsc_sinfo's rule with K floats more). */
+QSC_API int qsc_sgain(const float* S, const float* C, const float* J, const int32_t* perm,
+                      const float* w, const float* G, const qsc_model* m, int32_t R, int32_t K,
+                      int32_t P, int32_t Pp, int32_t criterion, float ridge, float* gain,
+                      int32_t* n_first, int32_t* n_bad, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Per-pixel damped Newton / Fisher-scoring fit of the loss fields for known spectra (qsc_sfit.hip).
  *   Conditional on C the likelihood separates over positions.  Position q minimises over
  *   s = S[q][0..R)

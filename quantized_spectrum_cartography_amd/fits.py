@@ -91,15 +91,22 @@ def check_confidence(kind, ridge, loss):
         raise ValueError('loss="squared" is not a likelihood: it has no Fisher information')
 
 
-def _confidence_pos(obs, S_pos, C, R, kind, ridge, map_std):
-    """confidence() on a position-order S (Pp, RP) and a device C (R, K)."""
+def _info_blocks_pos(obs, S_pos, C, R, kind):
+    """qsc_sinfo on a position-order S (Pp, RP) and a device C (R, K): J (Pp, RP, RP)."""
     desc, s_entries, _ = obs.layout(R)
     RP = obs.rank_pad(R)
-    dev = S_pos.device
-    J = torch.empty((obs.Pp, RP, RP), dtype=torch.float32, device=dev)
+    J = torch.empty((obs.Pp, RP, RP), dtype=torch.float32, device=S_pos.device)
     _lib.call("qsc_sinfo", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
               obs.model, R, _lib.ptr(S_pos), _lib.ptr(C), INFO_KINDS[kind], _lib.ptr(J),
               _lib.stream())
+    return J
+
+
+def _confidence_pos(obs, S_pos, C, R, kind, ridge, map_std):
+    """confidence() on a position-order S (Pp, RP) and a device C (R, K)."""
+    RP = obs.rank_pad(R)
+    dev = S_pos.device
+    J = _info_blocks_pos(obs, S_pos, C, R, kind)
     std_pos = torch.empty((obs.Pp, RP), dtype=torch.float32, device=dev)
     std_T = torch.empty((obs.K, obs.P), dtype=torch.float32, device=dev) if map_std else None
     nbad = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -145,6 +152,136 @@ def default_confidence_ridge(S, lambda_s):
     couples all pixels and is dropped.  0 for S = 0."""
     n = float(torch.linalg.norm(S.detach().to(torch.float32)))
     return float(lambda_s) / n if n > 0.0 else 0.0
+
+
+DESIGN_CRITERIA = {"D": 0, "A": 1, "V": 2}  # QSC_DESIGN_D, QSC_DESIGN_A, QSC_DESIGN_V
+
+
+@dataclass
+class DesignResult:
+    gain: torch.Tensor                  # (1, I, J), pixel order; +inf for a first look
+    first_look: int                     # pixels whose J_p + ridge I is not positive definite
+    degenerate: int                     # pixels whose block with the plan is not positive definite
+    entry_gain: Optional[torch.Tensor] = None  # (K, 1, I, J) or None (entry_gain=False)
+
+    def best(self, n):
+        """The n best sites: (n, 2) int64 rows (i, j) by descending gain, first looks (+inf)
+        first; equal gains in pixel order."""
+        flat = self.gain.reshape(-1)
+        n = int(n)
+        if not 1 <= n <= flat.numel():
+            raise ValueError("n must be in [1, %d], got %r" % (flat.numel(), n))
+        idx = torch.argsort(flat, descending=True, stable=True)[:n].to(torch.int64)
+        ncol = self.gain.shape[-1]
+        return torch.stack((idx // ncol, idx % ncol), dim=1)
+
+
+def check_design(criterion, kind, ridge, loss, weights, K):
+    """Validate the design arguments (before anything touches a device); the plan as an fp32
+    CPU tensor (K,) or None."""
+    if criterion not in DESIGN_CRITERIA:
+        raise ValueError("design criterion must be one of %s, got %r"
+                         % (sorted(DESIGN_CRITERIA), criterion))
+    if kind not in INFO_KINDS:
+        raise ValueError("design kind must be one of %s, got %r" % (sorted(INFO_KINDS), kind))
+    if not float(ridge) >= 0.0:
+        raise ValueError("the design ridge must be >= 0, got %r" % (ridge,))
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: it has no Fisher information')
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights).detach().to("cpu", torch.float32)
+    if tuple(w.shape) != (int(K),):
+        raise ValueError("weights must have shape (%d,), got %s" % (int(K), tuple(w.shape)))
+    if not bool((w >= 0).all()) or not bool(torch.isfinite(w).all()):
+        raise ValueError("the design weights must be finite and >= 0")
+    return w.contiguous()
+
+
+def _gain_pos(obs, S_pos, C, J, R, w, criterion, ridge):
+    """qsc_sgain on a position-order S (Pp, RP), a device C (R, K), the blocks J (Pp, RP, RP) and
+    a device plan w (K,) or None: (gain (Pp,), counters (2,) int32: first looks, degenerate)."""
+    RP = obs.rank_pad(R)
+    dev = S_pos.device
+    G = None
+    if criterion == "V":
+        G = torch.zeros((RP, RP), dtype=torch.float32, device=dev)
+        G[:R, :R] = C @ C.t()
+    gain = torch.empty(obs.Pp, dtype=torch.float32, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    _lib.call("qsc_sgain", _lib.ptr(S_pos), _lib.ptr(C), _lib.ptr(J), _lib.ptr(obs.perm),
+              _lib.ptr(w), _lib.ptr(G), obs.model, R, obs.K, obs.P, obs.Pp,
+              DESIGN_CRITERIA[criterion], float(ridge), _lib.ptr(gain), _lib.ptr(counters[0:1]),
+              _lib.ptr(counters[1:2]), _lib.stream())
+    return gain, counters
+
+
+def _entry_gain_pos(obs, S, C, J, R, w, ridge):
+    """1/2 log1p(w_k h_exp(t_kp) std_T[k, p]^2) (K, P), pixel order: the D gain of one reading of
+    bin k at pixel p, from qsc_info_std's std_T and qsc_entry_info (expected kind)."""
+    from ._model import get_tensor
+    from .utils import entry_information
+    dev = J.device
+    std_pos = torch.empty((obs.Pp, obs.rank_pad(R)), dtype=torch.float32, device=dev)
+    std_T = torch.empty((obs.K, obs.P), dtype=torch.float32, device=dev)
+    nbad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("qsc_info_std", _lib.ptr(J), _lib.ptr(obs.perm), R, obs.P, obs.Pp, _lib.ptr(C),
+              obs.K, float(ridge), _lib.ptr(std_pos), _lib.ptr(std_T), _lib.ptr(nbad),
+              _lib.stream())
+    T = get_tensor(S.reshape(R, 1, obs.I, obs.J), C).reshape(obs.K, obs.P)
+    h = entry_information(T, torch.zeros((), dtype=torch.int64, device=dev), obs.bin_boundaries,
+                          obs.noise_std, offset=obs.offset, log_model=obs.log_model,
+                          loss=obs.loss, kind="expected")
+    if obs.log_model:  # (an entry with t + offset <= 0 adds 0: qsc_sgain's rule)
+        h = torch.where(T + float(obs.offset) > 0.0, h, torch.zeros_like(h))
+    if w is not None:
+        h = h * w[:, None]
+    eg = 0.5 * torch.log1p(h * std_T * std_T)
+    return torch.where(torch.isinf(std_T), torch.full_like(eg, float("inf")), eg)
+
+
+def design(obs, S, C, weights=None, criterion="D", kind="expected", ridge=0.0, entry_gain=False):
+    """Where to measure next: the expected information gain, per pixel, of a planned batch of
+    readings at (S, C).
+
+    A plan is `weights` (K,), w_k >= 0 the number of readings planned in bin k (default: one of
+    every bin, "a sensor that reads every bin once").  With J_p the information block of the
+    readings already held (qmc.confidence's; `kind` selects how it is formed) and h_exp the Fisher
+    information of one reading, which does not depend on the code it will return,
+      A_p = sum_k w_k h_exp(T_hat[k, p]) c_k c_k^T,   M0 = J_p + ridge I,   M1 = M0 + A_p
+      criterion "D":  1/2 (logdet M1 - logdet M0)        the expected entropy reduction in nats
+                "A":  tr(M0^-1) - tr(M1^-1)              the reduction of sum_r var(S[r, p])
+                "V":  tr(G M0^-1) - tr(G M1^-1), G = C C^T: the reduction of sum_k var(T_hat[k, p]),
+                      the map's variance at the pixel
+    one HIP walk (qsc_sgain, include/qsc.h) after the one qsc_sinfo call that forms J.
+    Conditional on C the pixels are independent, so the gain of placing the plan at a pixel is
+    that pixel's figure alone and the best n distinct sites are the top n: result.best(n).
+    A pixel whose J_p + ridge I is not positive definite (no readings yet and ridge = 0) has gain
+    +inf, a first look, and is counted in first_look; one whose block is not positive definite
+    even with the plan has gain 0 and is counted in degenerate.  As in qmc.confidence, C is
+    treated as known.
+    entry_gain=True adds the "which bin" companion (K, 1, I, J): for a single extra reading of
+    bin k at pixel p, w_k of them, 1/2 log1p(w_k h_exp std_T[k, p]^2), the rank-one case of "D"
+    (+inf where std_T is); it materialises K x P values like confidence(map_std=True).
+    obs: the Observations; S (R,1,I,J) or (R,P), C (R,K).  Returns DesignResult(gain (1,I,J),
+    first_look, degenerate, entry_gain or None).  Raises ValueError for an unknown criterion or
+    kind, ridge < 0, negative weights or weights of another shape than (K,), or
+    obs.loss == "squared", before any GPU call."""
+    w = check_design(criterion, kind, ridge, getattr(obs, "loss", None), weights,
+                     getattr(obs, "K", C.shape[-1]))
+    R = S.shape[0]
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, obs.K).contiguous()
+    S_pos = obs.to_positions(S.detach().to(torch.float32).reshape(R, -1))
+    wd = w.to(Cd.device) if w is not None else None
+    J = _info_blocks_pos(obs, S_pos, Cd, R, kind)
+    gain, counters = _gain_pos(obs, S_pos, Cd, J, R, wd, criterion, ridge)
+    eg = None
+    if entry_gain:
+        Sd = _dev(S.detach().to(torch.float32)).reshape(R, obs.P)
+        eg = _entry_gain_pos(obs, Sd, Cd, J, R, wd, ridge).reshape(obs.K, 1, obs.I, obs.J)
+    first, bad = counters.tolist()
+    return DesignResult(gain=gain[obs.iperm().long()].reshape(1, obs.I, obs.J),
+                        first_look=first, degenerate=bad, entry_gain=eg)
 
 
 @dataclass

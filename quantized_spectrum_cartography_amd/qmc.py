@@ -24,10 +24,11 @@ from . import _lib
 from ._model import _dev, map_nmse
 # the post-solve estimators live in fits.py; qmc.fit_S etc. stay the user-facing spellings
 from .fits import (  # noqa: F401
-    INFO_KINDS, CalibrateResult, ConfidenceResult, FitCResult, FitNoiseResult, FitSResult,
-    FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos, _fit_s_smooth_pos,
-    _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_fit_noise,
-    check_polish_c, check_post_solve, confidence, default_confidence_ridge, fit_C, fit_noise,
+    DESIGN_CRITERIA, INFO_KINDS, CalibrateResult, ConfidenceResult, DesignResult, FitCResult,
+    FitNoiseResult, FitSResult, FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos,
+    _fit_s_smooth_pos, _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_design,
+    check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
+    design, fit_C, fit_noise,
     fit_S, fit_S_smooth, model_nll, post_solve, shifted_boundaries)
 from .fused import PassEngine, check_smooth
 from .obs import Observations
