@@ -13,6 +13,7 @@ dip.py entry points.  Module map (reference file in parentheses):
   fits                                                     post-solve estimators (confidence,
                                                            Newton fits, calibration), re-exported
                                                            by qmc
+  runs                                                     run driver, hipGraph capture, solver base
   dip                     (qmc/dip.py, empty upstream)     deep-image-prior solver
   obs, fused                                               packed observations, fused passes
   gram                    (backup/algorithms/NMF_SPA.m)    R x R normal equations (MFMA),

@@ -47,7 +47,7 @@ import torch
 
 from . import _lib
 from ._model import _dev
-from .qmc import issue_iterations, prepare_iterations, run_iterations
+from .runs import AlternatingSolver, cost_history
 
 
 def kslab_bounds(K, world, rank):
@@ -81,12 +81,16 @@ def _capturable(dist):
     except (RuntimeError, ValueError, AttributeError):
         return True
 
-class IJSlabSolver:
+class IJSlabSolver(AlternatingSolver):
     """Free-S alternating solver on one pixel block per rank (see module docstring)."""
+
+    graph_tolerant = True  # (a collective that cannot be captured: see runs.capture)
+    graph_state = ("S", "C", "mS", "vS", "mC", "vC", "red")
 
     def __init__(self, obs, S_init_local, C_init, dist, lambda_c=100.0, lambda_s=100.0,
                  lr_c=5e-3, lr_s=1e-2, betas=(0.9, 0.999), eps=1e-8, project_c=True,
                  hist_cap=1024, engine=None, fuse=True):
+        super().__init__()
         self.obs, self.dist = obs, dist
         R = S_init_local.shape[0]
         self.R = R
@@ -108,8 +112,6 @@ class IJSlabSolver:
         # S-step + next C-pass in one launch (qsc_scpass), as FreeSSolver
         sup = getattr(self.engine, "scpass_supported", None)
         self.fuse = bool(fuse) and sup is not None and bool(sup())
-        self._graphs = {}
-        self.graph_tolerant, self.graph_error = True, None  # see qmc._capture
         self.graph_capturable = _capturable(dist)
         if not self.graph_capturable:
             self.graph_error = "collectives over %s are not graph-capturable" % dist.get_backend()
@@ -134,22 +136,6 @@ class IJSlabSolver:
         self.engine.spass(self.S, self.C, 1, mS=self.mS, vS=self.vS, adam=self.adam_s,
                           lambda_s=self.lambda_s)
 
-    def iteration(self):
-        self.c_step()
-        self.s_step()
-
-    def issue(self, n):
-        issue_iterations(self, n)
-
-    def prepare(self, n):
-        prepare_iterations(self, n)
-
-    def run(self, n, use_graph=False):
-        run_iterations(self, n, use_graph)
-
-    def state(self):
-        return self.engine.read_state()
-
     def S_pixels(self):
         """This rank's pixel block of S, (R, 1, I_local, J)."""
         return self.obs.to_pixels(self.S, self.R).reshape(self.R, 1, self.obs.I, self.obs.J)
@@ -163,23 +149,23 @@ class IJSlabSolver:
         h = e.hist[: 4 * n].view(n, 4).clone()
         nll = h[:, :2].contiguous()
         self.dist.all_reduce(nll)
-        h = torch.cat([nll, h[:, 2:]], dim=1).double().cpu()
+        rows = torch.cat([nll, h[:, 2:]], dim=1).double().cpu().tolist()
         nsq_c_final = float((self.C.double() ** 2).sum().item())
-        costs_c, costs_s = [], []
-        for i in range(n):
-            nll_c, nll_s, nsq_c, nsq_s = h[i].tolist()
-            nsq_c_next = h[i + 1][2].item() if i + 1 < n else nsq_c_final
-            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + self.lambda_s * math.sqrt(nsq_s))
-            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_c_next) + self.lambda_s * math.sqrt(nsq_s))
-        return costs_c, costs_s
+        return cost_history(rows, nsq_c_final, self.lambda_c,
+                            [(self.lambda_s * math.sqrt(r[3]),) for r in rows])
 
 
-class KSlabSolver:
+class KSlabSolver(AlternatingSolver):
     """Free-S alternating solver on one K-slab per rank (see module docstring)."""
+
+    graph_tolerant = True  # (a collective that cannot be captured: see runs.capture)
+    graph_state = ("S", "C", "mS", "vS", "mC", "vC", "S_buf", "dS_buf", "dS_own")
+    _rs_norm = False
 
     def __init__(self, obs, S_init, C_init_local, dist, lambda_c=100.0, lambda_s=100.0,
                  lr_c=5e-3, lr_s=1e-2, betas=(0.9, 0.999), eps=1e-8, project_c=True,
                  hist_cap=1024, engine=None):
+        super().__init__()
         self.obs, self.dist = obs, dist
         R = S_init.shape[0]
         self.R = R
@@ -225,21 +211,19 @@ class KSlabSolver:
         self.adam_s = _lib.make_adam(lr_s, betas, eps, project_nonneg=False)
         self.lambda_c, self.lambda_s = float(lambda_c), float(lambda_s)
         self.engine.init_state(self.S)
-        self._graphs = {}
-        self.graph_tolerant, self.graph_error = True, None  # see qmc._capture
         self.graph_capturable = _capturable(dist)
         if not self.graph_capturable:
             self.graph_error = "collectives over %s are not graph-capturable" % dist.get_backend()
 
     def begin_run(self):
-        """(issue_iterations, at the start of every run): the run's first C-step all-reduces
+        """(AlternatingSolver.issue, at the start of every run): the run's first C-step all-reduces
         the C-pass's ||C_slab||^2, later ones take the one the reduce-scatter delivered."""
         self._rs_norm = False
 
     def c_step(self):
         e = self.engine
         e.cpass_nsq(self.S, self.C)  # + ||C_slab||^2 into nsq_c, + the slices' ||S||^2
-        if getattr(self, "_rs_norm", False):
+        if self._rs_norm:
             nsq = self.nsq_rs  # global ||C||^2 from the previous S-step's reduce-scatter
         else:
             self.dist.all_reduce(self.nsq_c)
@@ -259,22 +243,6 @@ class KSlabSolver:
         self.dist.all_gather_into_tensor(self.S_buf, self.S_buf[lo:lo + self.chunk])
         # (the next cpass_nsq rebuilds every slice's ||S_new||^2 partial from the gathered S)
         self._rs_norm = True
-
-    def iteration(self):
-        self.c_step()
-        self.s_step()
-
-    def issue(self, n):
-        issue_iterations(self, n)
-
-    def prepare(self, n):
-        prepare_iterations(self, n)
-
-    def run(self, n, use_graph=False):
-        run_iterations(self, n, use_graph)
-
-    def state(self):
-        return self.engine.read_state()
 
     def S_pixels(self):
         return self.obs.to_pixels(self.S, self.R).reshape(self.R, 1, self.obs.I, self.obs.J)
@@ -305,15 +273,9 @@ class KSlabSolver:
         h = e.hist[: 4 * n].view(n, 4).clone()
         nll = h[:, :2].contiguous()
         self.dist.all_reduce(nll)
-        h = torch.cat([nll, h[:, 2:]], dim=1).double().cpu()
+        rows = torch.cat([nll, h[:, 2:]], dim=1).double().cpu().tolist()
         nsq = torch.zeros(1, dtype=torch.float32, device=self.C.device)
         e.sumsq(self.C, nsq)
         self.dist.all_reduce(nsq)
-        nsq_c_final = float(nsq.item())
-        costs_c, costs_s = [], []
-        for i in range(n):
-            nll_c, nll_s, nsq_c, nsq_s = h[i].tolist()
-            nsq_c_next = h[i + 1][2].item() if i + 1 < n else nsq_c_final
-            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + self.lambda_s * math.sqrt(nsq_s))
-            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_c_next) + self.lambda_s * math.sqrt(nsq_s))
-        return costs_c, costs_s
+        return cost_history(rows, float(nsq.item()), self.lambda_c,
+                            [(self.lambda_s * math.sqrt(r[3]),) for r in rows])

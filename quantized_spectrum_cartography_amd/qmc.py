@@ -32,6 +32,10 @@ from .fits import (  # noqa: F401
     fit_S, fit_S_smooth, model_nll, post_solve, shifted_boundaries)
 from .fused import PassEngine, check_smooth
 from .obs import Observations
+# the run driver and the hipGraph mechanics live in runs.py; these spellings stay importable
+from .runs import (  # noqa: F401
+    GRAPH_MAX_ITERS, AlternatingSolver, abandon_capture, capture_stream, cost_history,
+    graph_chunks, quiesce_collectives, stream_capture_status)
 from .utils import LOG_OFFSET_7_ADJUSTED as LOG_OFFSET
 
 
@@ -55,251 +59,7 @@ class SolveResult:
     calibration: Optional["CalibrateResult"] = None
 
 
-# Longest run captured as one hipGraph; longer runs replay several (results are identical:
-# run(a) then run(b) equals run(a + b) bit for bit, tests/test_gpu_fused.py).
-GRAPH_MAX_ITERS = 1024
-
-
-def issue_iterations(solver, n):
-    """Kernel sequence of n outer iterations of a solver with c_step / s_step / iteration and,
-    when `solver.fuse`, fused_body (S-step i + C-pass i+1 in one launch, then C-step i+1's
-    finish): c_step, fused_body x (n-1), s_step -- two launches per iteration.
-
-    A solver with `chain` (FreeSSolver) ends a run with the fused launch instead of the
-    stand-alone S-step: its last S-step also runs the NEXT iteration's C-pass, whose partials
-    wait in the workspace (`ahead()`), and a following run starts with that C-pass's finish
-    instead of a C-pass of its own.  The op sequence of run(a) then run(b) is then exactly that
-    of run(a + b) -- c_step, fused_body x (a + b - 1), then the last S-step -- and every run of
-    n iterations issues n fused launches and n C-step finishes (the steady state), where the
-    stand-alone ends cost a C-pass and an S-pass per run."""
-    if hasattr(solver, "begin_run"):
-        solver.begin_run()
-    if getattr(solver, "fuse", False) and getattr(solver, "chain", False) and n >= 1:
-        if solver.ahead():
-            solver.c_finish()
-        else:
-            solver.c_step()
-        for _ in range(n - 1):
-            solver.fused_body()
-        solver.fused_last()
-    elif getattr(solver, "fuse", False) and n >= 2:
-        solver.c_step()
-        for _ in range(n - 1):
-            solver.fused_body()
-        solver.s_step()
-    else:
-        for _ in range(n):
-            solver.iteration()
-
-
-# RCCL's watchdog thread (torch ProcessGroupNCCL) polls the completion events of the eager
-# collectives still on its list every ~100 ms.  Polled while the collectives' stream is being
-# captured, such an event fails the query ("operation not permitted on an event last recorded in
-# a capturing stream") and the watchdog aborts the process -- seen on MI355X when a capture
-# followed an eager collective within milliseconds (profiles/r06/capture_watchdog_abort.log).
-# Before capturing collectives: drain the device, then let the watchdog retire its list.
-CAPTURE_QUIESCE_S = 0.3
-
-
-def quiesce_collectives(dist):
-    try:
-        nccl = dist is not None and dist.is_initialized() and dist.get_backend() == "nccl"
-    except (AttributeError, RuntimeError, ValueError):  # (a stand-in process group)
-        nccl = False
-    if not nccl:
-        return
-    import time
-    torch.cuda.synchronize()
-    time.sleep(CAPTURE_QUIESCE_S)
-
-
-def _capture(solver, n, tolerant):
-    """Capture run(n)'s kernel sequence into a hipGraph on a side stream.
-
-    A capture that fails part-way (an engine error, an illegal synchronisation, a collective
-    that cannot be captured) is abandoned cleanly: any capture still open on the side stream or
-    the current stream is ended and its graph destroyed, and the device is synchronised, BEFORE
-    anything else is issued -- work issued onto a stream that is still capturing would be
-    recorded instead of run, and a collective there fails ("operation not permitted when stream
-    is capturing").  Then, for a tolerant solver, the failure is recorded in `graph_error`, the
-    solver is marked not capturable and runs eagerly from then on; otherwise the error is
-    re-raised.  If the capture cannot be ended the error is always raised."""
-    quiesce_collectives(getattr(solver, "dist", None))
-    g = torch.cuda.CUDAGraph()
-    s = capture_stream()
-    caller = torch.cuda.current_stream()
-    s.wait_stream(caller)
-    mark = solver.chain_mark() if hasattr(solver, "chain_mark") else None
-    try:
-        with torch.cuda.stream(s):
-            # thread-local capture mode: other threads' HIP calls (RCCL's watchdog queries the
-            # events of collectives issued before the capture) must neither fail nor invalidate
-            # it -- in the default global mode the watchdog's query errors and aborts the process
-            with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                issue_iterations(solver, n)
-    except Exception as e:  # noqa: BLE001 - every failure takes the same clean-up path
-        if mark is not None:
-            solver.chain_restore(mark)
-        err = "%s: %s" % (type(e).__name__, e)
-        del g
-        abandon_capture(s, caller)  # raises if the caller's stream is left capturing
-        if not tolerant:
-            raise
-        solver.graph_error = err
-        solver.graph_capturable = False
-        warnings.warn("hipGraph capture failed; running eagerly (%s)" % err, RuntimeWarning)
-        return None
-    if mark is not None:
-        solver.chain_restore(mark)  # (capturing executes nothing: the device state is unchanged)
-    torch.cuda.current_stream().wait_stream(s)
-    _upload(g)
-    return g
-
-
-_hip = None
-
-
-def _hip_lib():
-    global _hip
-    if _hip is None:
-        import ctypes
-        h = ctypes.CDLL("libamdhip64.so")
-        h.hipGraphUpload.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        h.hipGraphUpload.restype = ctypes.c_int
-        h.hipStreamIsCapturing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        h.hipStreamIsCapturing.restype = ctypes.c_int
-        h.hipStreamEndCapture.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-        h.hipStreamEndCapture.restype = ctypes.c_int
-        h.hipGraphDestroy.argtypes = [ctypes.c_void_p]
-        h.hipGraphDestroy.restype = ctypes.c_int
-        h.hipGetLastError.argtypes = []
-        h.hipGetLastError.restype = ctypes.c_int
-        _hip = h
-    return _hip
-
-
-def capture_stream():
-    """A side stream that is not in a capture: torch hands out streams from a fixed pool
-    (round robin), and a stream whose capture was invalidated stays invalidated for good
-    (abandon_capture), so after a failed capture the pool can return such a stream again;
-    skip those."""
-    for _ in range(4 * 32 + 1):  # torch's pool holds 32 streams per priority
-        s = torch.cuda.Stream()
-        if stream_capture_status(s) == 0:
-            return s
-    raise RuntimeError("no side stream out of capture for hipGraph capture")
-
-
-def stream_capture_status(stream):
-    """0 = not capturing, 1 = capture active, 2 = capture invalidated (hipStreamCaptureStatus)."""
-    import ctypes
-    st = ctypes.c_int(0)
-    rc = _hip_lib().hipStreamIsCapturing(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(st))
-    return st.value if rc == 0 else -1  # -1: the query itself failed (treated as capturing)
-
-
-def abandon_capture(side, caller):
-    """Clean up after a capture on `side` failed: end (and discard) the capture still open on
-    it, clear the HIP error state and synchronise the device.  HIP leaves a stream whose
-    capture was invalidated in the invalidated state for good (measured, tools/probe/
-    capture_fail.py: hipStreamEndCapture returns an error and the status stays 2), so the side
-    stream is abandoned -- captures always use a fresh one -- and only the caller's stream,
-    where eager work continues, must be out of capture.  Raises RuntimeError otherwise."""
-    import ctypes
-    h = _hip_lib()
-    if stream_capture_status(side) != 0:
-        graph = ctypes.c_void_p(None)
-        h.hipStreamEndCapture(ctypes.c_void_p(side.cuda_stream), ctypes.byref(graph))
-        if graph.value:
-            h.hipGraphDestroy(graph)
-    h.hipGetLastError()  # clear the (non-sticky) capture error
-    if stream_capture_status(caller) != 0:
-        raise RuntimeError("a failed hipGraph capture left the caller's stream capturing")
-    torch.cuda.synchronize()
-    h.hipGetLastError()
-
-
-def _upload(g):
-    """hipGraphUpload the instantiated graph now, so that its first replay does not pay the
-    upload (a fixed ~tens of us that would otherwise land in a short timed run)."""
-    try:
-        ex = g.raw_cuda_graph_exec()
-        rc = _hip_lib().hipGraphUpload(ex, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("hipGraphUpload returned %d" % rc)
-        torch.cuda.current_stream().synchronize()
-    except (OSError, AttributeError, RuntimeError) as e:  # upload is an optimisation only
-        warnings.warn("hipGraphUpload skipped (%s)" % e, RuntimeWarning)
-
-
-def graph_for(solver, n):
-    """The hipGraph of the exact kernel sequence of run(n) from the solver's current state
-    (captured once per n and, for a chaining solver, per whether a C-pass is ahead)."""
-    graphs = solver.__dict__.setdefault("_graphs", {})
-    if getattr(solver, "graph_capturable", True) is False:
-        return None  # eager (the reason is in solver.graph_error)
-    key = (n, solver.ahead()) if hasattr(solver, "ahead") else n
-    # a graph holds its tensors' addresses: a solver whose state tensors were swapped for others
-    # (sol.C = ...) captures anew instead of replaying into the old storage
-    ptrs = tuple(t.data_ptr() for t in (getattr(solver, a, None) for a in _STATE_TENSORS)
-                 if isinstance(t, torch.Tensor))
-    if solver.__dict__.get("_graph_ptrs") != ptrs:
-        graphs.clear()
-        solver._graph_ptrs = ptrs
-    if key not in graphs:
-        graphs[key] = _capture(solver, n, getattr(solver, "graph_tolerant", False))
-    return graphs[key]
-
-
-_STATE_TENSORS = ("S", "C", "mS", "vS", "mC", "vC", "S_buf", "dS_buf", "dS_own", "red")
-
-
-def graph_chunks(n):
-    """The graph lengths run(n) replays, in order: 1024-iteration chunks, then the remainder."""
-    out = []
-    while n > 0:
-        m = min(n, GRAPH_MAX_ITERS)
-        out.append(m)
-        n -= m
-    return out
-
-
-def prepare_iterations(solver, n):
-    """Capture (without executing) every graph that run(n, use_graph=True) will replay, so a
-    later timed run(n) captures, instantiates and uploads nothing."""
-    if not hasattr(solver, "chain_mark"):
-        for m in sorted(set(graph_chunks(n))):
-            graph_for(solver, m)
-        return
-    # A chaining solver's graphs are keyed by whether a C-pass is ahead: run(n) from the current
-    # state replays (m, ahead()) for its first chunk and (m, True) for the later ones, and a later
-    # run(n) starts with a C-pass ahead.  Capture both entry forms of every chunk size, so no
-    # later run(n) captures anything whatever state it starts from.
-    mark = solver.chain_mark()
-    for m in sorted(set(graph_chunks(n))):
-        for a in (False, True):
-            if solver.chain_force(a):
-                graph_for(solver, m)
-    solver.chain_restore(mark)
-
-
-def run_iterations(solver, n, use_graph):
-    """run(n): eager, or as replays of whole-run hipGraphs (one replay when n <= 1024), so the
-    device work of a timed run(n) does not depend on how earlier runs were split."""
-    if not (use_graph and torch.cuda.is_available() and solver.S.is_cuda):
-        issue_iterations(solver, n)
-        return
-    for m in graph_chunks(n):
-        g = graph_for(solver, m)
-        if g is None:
-            issue_iterations(solver, m)
-        else:
-            g.replay()
-            if hasattr(solver, "chain_replayed"):
-                solver.chain_replayed()
-
-
-class FreeSSolver:
+class FreeSSolver(AlternatingSolver):
     """Device-resident free-S alternating solver over one Observations set.
 
     State (position-ordered S, Adam moments, step counters, ||S||^2, NLLs) lives on the GPU.
@@ -310,10 +70,13 @@ class FreeSSolver:
     n in a hipGraph (torch.cuda.CUDAGraph) and replayed; `prepare(n)` captures it ahead.
     """
 
+    graph_state = ("S", "C", "mS", "vS", "mC", "vC")
+
     def __init__(self, obs, S_init, C_init, lambda_c=100.0, lambda_s=100.0, lr_c=5e-3, lr_s=1e-2,
                  betas=(0.9, 0.999), eps=1e-8, project_c=True, hist_cap=1024, fuse=True,
                  T_true=None, nmse_every=0, project_s=None, chain=True, smooth=0.0,
                  smooth_kind="quad", smooth_delta=None):
+        super().__init__()
         self.smooth = check_smooth(smooth, smooth_kind, smooth_delta)
         self.smooth_kind, self.smooth_delta = smooth_kind, smooth_delta
         self.obs = obs
@@ -337,12 +100,11 @@ class FreeSSolver:
         self.lambda_c, self.lambda_s = float(lambda_c), float(lambda_s)
         self.engine.init_state(self.S)
         self.fuse = bool(fuse) and self.engine.scpass_supported()
-        # chain: runs end with the fused launch (issue_iterations); `_ahead` says that the
+        # chain: runs end with the fused launch (AlternatingSolver.issue); `_ahead` says that the
         # workspace holds the C-pass of the next iteration at the current S, C (valid while
         # neither tensor was modified by torch since: their version counters)
         self.chain = bool(chain)
         self._ahead, self._ahead_ver = False, None
-        self._graphs = {}
         if self.smooth > 0.0:
             # smoothness prior smooth * R(S) (qsc_smooth_grad): the S-step becomes gradient pass
             # -> prior gradient -> Adam (three launches and a one-block finish), so neither the
@@ -350,6 +112,7 @@ class FreeSSolver:
             self.fuse = False
             self.chain = False
             self.dS_buf = torch.zeros_like(self.S)
+            self.graph_state += ("dS_buf",)
             obs.neighbors()  # (built here, outside any capture)
             self.engine._smooth_bufs()
         # map NMSE after every `nmse_every`-th S-step, on the device inside the iteration
@@ -384,7 +147,7 @@ class FreeSSolver:
         e.spass(self.S, self.C, 1, mS=self.mS, vS=self.vS, adam=self.adam_s, lambda_s=self.lambda_s)
         self._track()
 
-    # ---- run chaining (issue_iterations) ----
+    # ---- run chaining (AlternatingSolver.issue) ----
     def _chain_key(self):
         """What a C-pass left ahead depends on: S and C (their storage and torch version
         counters: an in-place torch write, or a fresh tensor swapped in) and the workspace it
@@ -415,10 +178,10 @@ class FreeSSolver:
         if self.chain and self.fuse:
             self._ahead, self._ahead_ver = True, self._chain_key()
 
-    def chain_mark(self):
+    def capture_mark(self):
         return (self._ahead, self._ahead_ver, self.engine.gen)
 
-    def chain_restore(self, mark):
+    def capture_restore(self, mark):
         # (a capture issues launches without executing them: the engine's generation returns to
         # its value before the capture, so the captured run does not invalidate the state)
         self._ahead, self._ahead_ver, self.engine.gen = mark
@@ -431,9 +194,8 @@ class FreeSSolver:
             self._ahead = False
         return self.ahead() == bool(ahead)
 
-    def iteration(self):
-        self.c_step()
-        self.s_step()
+    def graph_key(self, n):
+        return (n, self.ahead())
 
     def fused_body(self):
         """S-step i fused with C-pass i+1, then C-step i+1's finish (needs a C-step before)."""
@@ -461,23 +223,7 @@ class FreeSSolver:
         h = self._nmse_hist[:n].cpu()
         return [float((a / b) ** 0.5) if b > 0 else float("nan") for a, b in h.tolist()]
 
-    def issue(self, n):
-        """Enqueue the kernel sequence of n outer iterations (no host sync)."""
-        issue_iterations(self, n)
-
-    def prepare(self, n):
-        """Capture the kernel sequence of run(n) in a hipGraph now (capture executes nothing),
-        so that a later run(n, use_graph=True) is graph replays only (one when n <= 1024)."""
-        prepare_iterations(self, n)
-
-    def run(self, n, use_graph=False):
-        """Enqueue n outer iterations (no host sync)."""
-        run_iterations(self, n, use_graph)
-
     # ---- results --------------------------------------------------------------------------
-    def state(self):
-        return self.engine.read_state()
-
     def S_pixels(self):
         return self.obs.to_pixels(self.S, self.R).reshape(self.R, 1, self.obs.I, self.obs.J)
 
@@ -485,21 +231,15 @@ class FreeSSolver:
         self.engine.flush()  # settle the last S-pass (its history row)
         st = self.state()
         n = min(int(st["iter"]), self.engine.hist_cap)
-        h = self.engine.hist[: 4 * n].view(n, 4).double().cpu()
+        rows = self.engine.hist[: 4 * n].view(n, 4).double().cpu().tolist()
         nsq_c_final = float((self.C.double() ** 2).sum().item())
         # smooth * R(S) at the S both steps of iteration i were evaluated with (the S before
         # S-step i), recorded by that S-step's qsc_smooth_grad
         pen = self.engine.smooth_history() if self.smooth > 0.0 else []
-        costs_c, costs_s = [], []
-        for i in range(n):
-            nll_c, nll_s, nsq_c, nsq_s = h[i].tolist()
-            nsq_c_next = h[i + 1][2].item() if i + 1 < n else nsq_c_final
-            prior = self.smooth * pen[i] if i < len(pen) else 0.0
-            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + self.lambda_s * math.sqrt(nsq_s)
-                           + prior)
-            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_c_next) + self.lambda_s * math.sqrt(nsq_s)
-                           + prior)
-        return costs_c, costs_s
+        return cost_history(rows, nsq_c_final, self.lambda_c,
+                            [(self.lambda_s * math.sqrt(r[3]),
+                              self.smooth * pen[i] if i < len(pen) else 0.0)
+                             for i, r in enumerate(rows)])
 
 
 def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, offset=None,
@@ -693,7 +433,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
 GEN_GRAPH_ITERS = 32
 
 
-class GeneratorSolver:
+class GeneratorSolver(AlternatingSolver):
     """S = generator(Z) alternating solver (qmc/qmc.ipynb :541-634) as a device-resident op
     sequence that is captured in hipGraphs (the DIP solver of dip.solve, the GAN path of solve).
 
@@ -717,10 +457,13 @@ class GeneratorSolver:
     eagerly from then on."""
 
     WARMUP = 1
+    graph_tolerant = True
+    graph_iters = GEN_GRAPH_ITERS
 
     def __init__(self, obs, generator, Z_init, C_init, R, lambda_c=100.0, lambda_s=100.0,
                  lr_c=5e-3, lr_s=1e-2, betas=(0.9, 0.999), eps=1e-8, project_c=True,
                  params=None, optimize_z=True, hist_cap=1024):
+        super().__init__()
         dev = obs.device
         self.obs, self.net, self.R = obs, generator, R
         self.I, self.J = obs.I, obs.J
@@ -769,10 +512,8 @@ class GeneratorSolver:
         self.S_last = S0.detach()
         self.done = 0
         self._eager_done = 0
-        self._graphs = {}
-        self._pool = None
-        self.graph_error = None
-        self.graph_capturable = True
+        # (the chunk graphs share one memory pool)
+        self.graph_pool = torch.cuda.graph_pool_handle() if self.C.is_cuda else None
 
     # ---- one iteration (capturable) -----------------------------------------------------
     def c_step(self):
@@ -807,103 +548,44 @@ class GeneratorSolver:
             self.ctr += 1
         self.S_last = S.detach()
 
-    def iteration(self):
-        self.c_step()
-        self.s_step()
-
     # ---- runs ---------------------------------------------------------------------------
-    def _capture(self, m):
-        g = torch.cuda.CUDAGraph()
-        s = capture_stream()
-        caller = torch.cuda.current_stream()
-        s.wait_stream(caller)
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        gen0 = self.engine.gen
-        try:
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, pool=self._pool,
-                                      capture_error_mode="thread_local"):
-                    for _ in range(m):
-                        self.iteration()
-        except Exception as e:  # noqa: BLE001 - every failure takes the same clean-up path
-            del g
-            abandon_capture(s, caller)
-            self.engine.gen = gen0
-            self.graph_error = "%s: %s" % (type(e).__name__, e)
-            self.graph_capturable = False
-            warnings.warn("hipGraph capture of the generator iteration failed; running eagerly "
-                          "(%s)" % self.graph_error, RuntimeWarning)
-            return None
-        self.engine.gen = gen0
-        caller.wait_stream(s)
-        _upload(g)
-        return g
-
-    def _graph(self, m):
-        if not self.graph_capturable:
-            return None
-        if m not in self._graphs:
-            self._graphs[m] = self._capture(m)
-        return self._graphs[m]
-
     def prepare(self, n):
         """Capture (without executing) the chunk graphs run(n) will replay.  Needs the WARMUP
         eager iterations done (they create the optimizer state outside capture)."""
         if self._eager_done < self.WARMUP:
             raise RuntimeError("prepare() after %d eager iterations (run them first)" % self.WARMUP)
-        for m in sorted(set(_gen_chunks(n))):
-            self._graph(m)
+        super().prepare(n)
 
     def run(self, n, use_graph=True):
-        """Enqueue n iterations (no host sync)."""
-        use_graph = use_graph and torch.cuda.is_available() and self.C.is_cuda
-        while n > 0 and (self._eager_done < self.WARMUP or not use_graph):
-            self.iteration()
-            self._eager_done += 1
-            self.done += 1
-            n -= 1
-        for m in _gen_chunks(n):
-            g = self._graph(m)
-            if g is None:
-                for _ in range(m):
-                    self.iteration()
-            else:
-                g.replay()
-            self.done += m
+        """Enqueue n iterations (no host sync): the WARMUP iterations still to do (all n
+        without use_graph) eagerly, the rest as chunk-graph replays."""
+        use_graph = use_graph and self._on_gpu()
+        eager = min(n, max(self.WARMUP - self._eager_done, 0)) if use_graph else n
+        super().run(eager)
+        self._eager_done += eager
+        super().run(n - eager, use_graph=True)
+        self.done += n
+
+    def capture_mark(self):
+        return self.engine.gen
+
+    def capture_restore(self, mark):
+        self.engine.gen = mark  # (a capture issues launches without executing them)
 
     # ---- results --------------------------------------------------------------------------
     def S_pixels(self):
         """The last S-step's generator output S (R, 1, I, J)."""
         return self.S_last
 
-    def state(self):
-        return self.engine.read_state()
-
     def history(self):
         """Per-iteration costs (qmc/qmc.ipynb :573, :631): C-step cost at the C it
         differentiates, S-step cost at the updated C (both with lambda_s ||Z|| of the S-step's
         Z), from the device history rows (one synchronisation)."""
         n = min(self.done, self.hist_cap)
-        h = self.engine.hist[: 4 * n].view(n, 4).double().cpu()
-        z = self.zreg[:n].double().cpu()
+        rows = self.engine.hist[: 4 * n].view(n, 4).double().cpu().tolist()
+        z = self.zreg[:n].double().cpu().tolist()
         nsq_c_final = float((self.C.double() ** 2).sum().item())
-        costs_c, costs_s = [], []
-        for i in range(n):
-            nll_c, nll_s, nsq_c = h[i][0].item(), h[i][1].item(), h[i][2].item()
-            nsq_next = h[i + 1][2].item() if i + 1 < n else nsq_c_final
-            costs_c.append(nll_c + self.lambda_c * math.sqrt(nsq_c) + z[i].item())
-            costs_s.append(nll_s + self.lambda_c * math.sqrt(nsq_next) + z[i].item())
-        return costs_c, costs_s
-
-
-def _gen_chunks(n):
-    out = []
-    while n > 0:
-        m = min(n, GEN_GRAPH_ITERS)
-        out.append(m)
-        n -= m
-    return out
+        return cost_history(rows, nsq_c_final, self.lambda_c, [(zi,) for zi in z])
 
 
 def split_holdout(Y, Wx, frac, seed=0):

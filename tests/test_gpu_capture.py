@@ -77,18 +77,19 @@ def test_failed_capture_raises_for_intolerant_solver_and_stream_stays_usable():
 def test_prepare_captures_every_chunk(monkeypatch):
     """run(n) after prepare(n) captures nothing new, also when n spans several graph chunks
     (bench's timed region must be replay only)."""
-    from quantized_spectrum_cartography_amd import qmc
-    monkeypatch.setattr(qmc, "GRAPH_MAX_ITERS", 4)
+    from quantized_spectrum_cartography_amd import runs
+    from quantized_spectrum_cartography_amd.qmc import FreeSSolver
+    monkeypatch.setattr(FreeSSolver, "graph_iters", 4)
     d = _random_case(73, 4, 64, 64, 64)
     sol = _solver(d)
     sol.prepare(10)
     # chunks 4, 4, 2, each captured in both entry forms: without a C-pass ahead (a first run)
     # and with the C-pass the previous chunk's or run's last fused launch left ahead
-    # (qmc.issue_iterations) -- so neither this run(10) nor a later one captures (ADVICE r5)
+    # (AlternatingSolver.issue) -- so neither this run(10) nor a later one captures (ADVICE r5)
     assert sorted(sol._graphs) == [(2, False), (2, True), (4, False), (4, True)]
     calls = []
-    orig = qmc._capture
-    monkeypatch.setattr(qmc, "_capture", lambda *a: calls.append(a) or orig(*a))
+    orig = runs.capture
+    monkeypatch.setattr(runs, "capture", lambda *a: calls.append(a) or orig(*a))
     sol.run(10, use_graph=True)
     sol.run(10, use_graph=True)
     assert calls == []

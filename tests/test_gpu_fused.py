@@ -435,8 +435,8 @@ def test_generator_solver_graph_equals_eager(optimize):
     import copy
     from quantized_spectrum_cartography_amd import dip, qmc
     dec, Z0, C0, Y, Wx, b, off = _dip256_case(seed=4)
-    old = qmc.GEN_GRAPH_ITERS
-    qmc.GEN_GRAPH_ITERS = 4  # two chunk graphs (4 + 2) after the eager iteration
+    old = qmc.GeneratorSolver.graph_iters
+    qmc.GeneratorSolver.graph_iters = 4  # two chunk graphs (4 + 2) after the eager iteration
     try:
         out = []
         for g in (False, True):
@@ -445,7 +445,7 @@ def test_generator_solver_graph_equals_eager(optimize):
                           lr_s=1e-3, optimize=optimize, use_graph=g)
             out.append(r)
     finally:
-        qmc.GEN_GRAPH_ITERS = old
+        qmc.GeneratorSolver.graph_iters = old
     a, c = out
     assert c.graph_error is None and len(c.solver._graphs) == (2 if optimize == "z" else 1)
     tol = 1e-5 if optimize == "z" else 5e-3

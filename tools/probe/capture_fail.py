@@ -1,5 +1,5 @@
 """Probe: HIP stream state after a hipGraph capture invalidated by a synchronisation (what
-qmc.abandon_capture must handle).  Prints hipStreamIsCapturing (rc, status) per stream."""
+runs.abandon_capture must handle).  Prints hipStreamIsCapturing (rc, status) per stream."""
 import ctypes
 import torch
 
