@@ -573,6 +573,70 @@ QSC_API int qsc_sgain(const float* S, const float* C, const float* J, const int3
                       int32_t* n_first, int32_t* n_bad, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-position goodness of fit and level-shift score tests (qsc_check.hip): are the readings of
+ * a position -- a physical sensor -- consistent with the fitted model?
+ *   Take position q with entries e = (k, y); pad entries are skipped.  Let t = s_q . c_k, x = t
+ *   (linear model) or log(t + offset), dxdt = 1 or 1 / (t + offset).  P_b, P_b' of bin
+ *   b = 0 .. nbins - 1 are qsc_sinfo's (the same device function, mirroring and saturation rules);
+ *   bins with P_b == 0 are dropped from every sum over b.  Per entry:
+ *     l   = -log max(P_y, FLT_MIN)
+ *     H   = -sum_b P_b log P_b                   the model's own expectation of l
+ *     var = max(sum_b P_b log^2 P_b - H^2, 0)    its variance
+ *     g_x = -P_y' / P_y                          the score in x at the observed code; 0 if P_y == 0
+ *     h_x = sum_b P_b'^2 / P_b                   QSC_INFO_EXPECTED, as qsc_sinfo
+ *   Per position, with `fitted` 0 or 1:
+ *     D   = sum_e (l - H)        V = sum_e var        n = entries used
+ *     u   = sum_e g_x            Ixx = sum_e h_x
+ *     g   = sum_e g_x dxdt c_k + ridge s_q            (R; the S-gradient of qsc_sfit's objective)
+ *     v   = sum_e h_x dxdt c_k                        (R; expected cross information of shift and s)
+ *     J   = sum_e h_x dxdt^2 c_k c_k^T + ridge I      (R x R; qsc_sinfo's expected block)
+ *     fitted = 0:  u* = u,                I* = Ixx
+ *     fitted = 1:  u* = u - v^T J^-1 g,   I* = Ixx - v^T J^-1 v   (efficient score, Schur complement)
+ *   With J = L L^T one forward substitution per right-hand side is enough: a = L^-1 v, b = L^-1 g,
+ *   I* = Ixx - a . a, u* = u - a . b.
+ *   Under the model at the true (S, C) and with fitted = 0, D has mean 0 and variance V exactly,
+ *   for any n, and u has mean 0 and variance Ixx exactly (the Fisher identity).  With fitted = 1,
+ *   u* / sqrt(I*) is Neyman's C(alpha) statistic for a shift delta of the position's received level
+ *   (x -> x + delta) with s_q the nuisance parameter; it is valid to first order where s_q is not
+ *   exactly the conditional MLE, because g is carried.  D is not corrected for the fit: after a fit
+ *   of s_q to the same readings it is biased low by about R / 2; on held-out readings with
+ *   fitted = 0 it is exact.  C is treated as known, as in qsc_sinfo.
+ *   The flag word of a position:
+ *     QSC_CHECK_UNTESTABLE  fitted = 1 and J has a pivot that is not positive (qsc_info_std's
+ *                           rule) or I* <= 1e-4 Ixx: the shift is confounded with s_q, or I* is
+ *                           rounding noise (the fp32 quadratic form carries about
+ *                           R 2^-24 Ixx ~ 1e-6 Ixx at R = 16; the guard is 100 x that).  u* and I*
+ *                           are written as 0.  A position without entries is untestable.
+ *     QSC_CHECK_INVALID     log model: an entry has t + offset <= 0.  All four statistics are
+ *                           written as 0, n counts the remaining entries, and the untestable bit
+ *                           is left clear (the shift test was not evaluated).
+ *     QSC_CHECK_SATURATED   an entry's fp32 P_y is 0: its l is -log FLT_MIN and it adds 0 to g_x,
+ *                           g and u (its H, var and h_x are added as usual).
+ *   Padding positions (perm[q] < 0) get all zeros and flag 0.  Nothing is ever NaN.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_CHECK_UNTESTABLE 1
+#define QSC_CHECK_INVALID 2
+#define QSC_CHECK_SATURATED 4
+/* stat[Pp][4] = (D, V, u*, I*) (fp32, one 16-byte store per position), count[Pp] = n and
+ * flags[Pp], all in position order, from one walk over the S-format lists of any layout
+ * qsc_obs_fill produces (qsc_sinfo's walk: two lanes per position, alternate entry pairs in list
+ * order, one lane exchange); S in position order [Pp][RP], C [R][K], perm[Pp] as qsc_info_std.
+ * Per-entry terms are fp32; D and V are summed in fp64 (l - H cancels), the rest in fp32.  No
+ * workspace, no allocation, no atomics: two calls agree bit for bit; stream-ordered, capturable.
+ * QSC_EINVAL for m->loss == QSC_LOSS_SQUARED or a bad model, a layout / model mismatch
+ * (qsc_sinfo's checks), ridge < 0 or NaN, or fitted outside {0, 1}; QSC_EUNSUPPORTED by
+ * qsc_sinfo's LDS rule. */
+QSC_API int qsc_scheck(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
+                       const int64_t* s_off, const int32_t* perm, const qsc_model* m, int32_t R,
+                       const float* S, const float* C, int32_t fitted, float ridge, float* stat,
+                       int32_t* count, int32_t* flags, void* stream);
+/* Elementwise terms of the walk above at the map value t = T[i] and the code Y[i] (the same device
+ * function): out[5][n] (fp32) = l - H, var, g_x, h_x, dxdt.  Y outside [0, nbins) is clamped as
+ * qsc_entry_info clamps it; in the log model an element with t + offset <= 0 gets five zeros. */
+QSC_API int qsc_entry_check(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
+                            float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Per-pixel damped Newton / Fisher-scoring fit of the loss fields for known spectra (qsc_sfit.hip).
  *   Conditional on C the likelihood separates over positions.  Position q minimises over
  *   s = S[q][0..R)

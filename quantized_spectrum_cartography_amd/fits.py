@@ -1,5 +1,5 @@
-"""The post-solve estimators (not in the reference): confidence, the Newton fits fit_S, fit_C,
-fit_S_smooth and fit_noise, model_nll, calibrate, and the stage of solve() that runs them on its
+"""The post-solve estimators (not in the reference): confidence, design, check_fit, the Newton
+fits fit_S, fit_C, fit_S_smooth and fit_noise, model_nll, calibrate, and the stage of solve() that runs them on its
 result (check_post_solve, post_solve).  Every public function validates its arguments before
 anything touches a device; the `_*_pos` drivers take a position-order S (Pp, RP) and device
 tensors.  qmc re-exports the names: qmc.fit_S etc. stay the user-facing spellings.
@@ -282,6 +282,161 @@ def design(obs, S, C, weights=None, criterion="D", kind="expected", ridge=0.0, e
     first, bad = counters.tolist()
     return DesignResult(gain=gain[obs.iperm().long()].reshape(1, obs.I, obs.J),
                         first_look=first, degenerate=bad, entry_gain=eg)
+
+
+CHECK_UNTESTABLE, CHECK_INVALID, CHECK_SATURATED = 1, 2, 4  # QSC_CHECK_* (include/qsc.h)
+FLAG_WHICH = ("shift", "fit", "either")
+
+
+def _z(num, den):
+    """num / sqrt(den) where den > 0, else 0: the one rule every z of CheckResult is formed by."""
+    ok = den > 0
+    return torch.where(ok, num / torch.sqrt(torch.where(ok, den, torch.ones_like(den))),
+                       torch.zeros_like(num))
+
+
+@dataclass
+class CheckResult:
+    n: torch.Tensor                     # (I, J) int32: readings used at the pixel
+    z_fit: torch.Tensor                 # (I, J) D / sqrt(V) (0 where V == 0)
+    z_shift: torch.Tensor               # (I, J) -u* / sqrt(I*): positive, the sensor reads high
+    shift: torch.Tensor                 # (I, J) -u* / I*: one-step estimate of delta, model domain
+    flags: torch.Tensor                 # (I, J) int32: 1 untestable, 2 invalid, 4 saturated
+    D: torch.Tensor                     # (I, J) sum (l - H)
+    V: torch.Tensor                     # (I, J) sum var
+    u: torch.Tensor                     # (I, J) u* (the efficient score with fitted=True)
+    info: torch.Tensor                  # (I, J) I*
+    untestable: int = 0                 # pixels with flag bit 1
+    invalid: int = 0                    # ... bit 2
+    saturated: int = 0                  # ... bit 4
+    z_fit_total: float = 0.0            # sum D / sqrt(sum V) over the valid pixels
+
+    def testable(self, which="shift"):
+        """(I, J) bool: the pixels the `which` test can judge -- never an untestable (shift) or
+        invalid one, and only where the statistic's variance is positive."""
+        if which not in FLAG_WHICH:
+            raise ValueError("which must be one of %s, got %r" % (FLAG_WHICH, which))
+        valid = (self.flags & CHECK_INVALID) == 0
+        t_shift = valid & ((self.flags & CHECK_UNTESTABLE) == 0) & (self.info > 0)
+        t_fit = valid & (self.V > 0)
+        return {"shift": t_shift, "fit": t_fit, "either": t_shift | t_fit}[which]
+
+    def flagged(self, alpha=0.01, which="shift", method="bonferroni"):
+        """(I, J) bool mask of the pixels whose statistic rejects the model at family-wise level
+        alpha: a two-sided normal test, |z| > -ndtri(alpha / (2 m)), m the number of testable
+        pixels (Bonferroni).  which="shift" tests z_shift, "fit" z_fit, "either" both at alpha / 2
+        each.  Untestable and invalid pixels are never flagged."""
+        if method != "bonferroni":
+            raise ValueError('method must be "bonferroni", got %r' % (method,))
+        if not 0.0 < float(alpha) < 1.0:
+            raise ValueError("alpha must be in (0, 1), got %r" % (alpha,))
+        if which not in FLAG_WHICH:
+            raise ValueError("which must be one of %s, got %r" % (FLAG_WHICH, which))
+        if which == "either":
+            return (self.flagged(float(alpha) / 2, "shift", method)
+                    | self.flagged(float(alpha) / 2, "fit", method))
+        ok = self.testable(which)
+        m = int(ok.sum())
+        if m == 0:
+            return torch.zeros_like(ok)
+        z = self.z_shift if which == "shift" else self.z_fit
+        crit = -torch.special.ndtri(torch.tensor(float(alpha) / (2.0 * m), dtype=torch.float64))
+        return ok & (z.double().abs() > crit.to(z.device))
+
+
+def check_check_fit(loss, ridge):
+    """Validate the check_fit arguments (before anything touches a device)."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: there is no model to check')
+    if not float(ridge) >= 0.0:
+        raise ValueError("the check_fit ridge must be >= 0, got %r" % (ridge,))
+
+
+def _check_pos(obs, S_pos, C, R, fitted, ridge, stat=None, count=None, flags=None):
+    """qsc_scheck on a position-order S (Pp, RP) and a device C (R, K): (stat (Pp, 4) = D, V, u*,
+    I*, count (Pp,) int32, flags (Pp,) int32), all on the device; nothing is read back."""
+    desc, s_entries, _ = obs.layout(R)
+    dev = S_pos.device
+    if stat is None:
+        stat = torch.empty((obs.Pp, 4), dtype=torch.float32, device=dev)
+        count = torch.empty(obs.Pp, dtype=torch.int32, device=dev)
+        flags = torch.empty(obs.Pp, dtype=torch.int32, device=dev)
+    _lib.call("qsc_scheck", desc, _lib.ptr(s_entries), _lib.ptr(obs.s_width), _lib.ptr(obs.s_off),
+              _lib.ptr(obs.perm), obs.model, R, _lib.ptr(S_pos), _lib.ptr(C), 1 if fitted else 0,
+              float(ridge), _lib.ptr(stat), _lib.ptr(count), _lib.ptr(flags), _lib.stream())
+    return stat, count, flags
+
+
+def check_result(D, V, u, info, n, flags):
+    """CheckResult from the four statistics, the counts and the flag words (same-shaped tensors):
+    the z's, the one-step shift, the flag counts and the total are formed here and nowhere else."""
+    ok = info > 0
+    shift = torch.where(ok, -u / torch.where(ok, info, torch.ones_like(info)),
+                        torch.zeros_like(u))
+    valid = (flags & CHECK_INVALID) == 0
+    sD = float((D.double() * valid).sum())
+    sV = float((V.double() * valid).sum())
+    return CheckResult(
+        n=n, z_fit=_z(D, V), z_shift=_z(-u, info), shift=shift, flags=flags, D=D, V=V, u=u,
+        info=info, untestable=int(((flags & CHECK_UNTESTABLE) != 0).sum()),
+        invalid=int(((flags & CHECK_INVALID) != 0).sum()),
+        saturated=int(((flags & CHECK_SATURATED) != 0).sum()),
+        z_fit_total=sD / math.sqrt(sV) if sV > 0.0 else 0.0)
+
+
+def check_fit(obs, S, C, fitted=True, ridge=0.0):
+    """Are the readings consistent with the fitted model, and which sensors are not?  Per pixel
+    (a pixel of the map is a physical sensor) a goodness-of-fit statistic and a score test for a
+    level shift of that sensor alone, from one HIP walk over the packed lists (qsc_scheck;
+    include/qsc.h has every formula).
+
+    Per reading, with P_b the model's probability of code b at the map value: l = -log P_y, its
+    expectation H = -sum_b P_b log P_b and variance var under the model, the score g_x = -P_y'/P_y
+    in the model domain x and its Fisher information h_x.  Per pixel
+      D = sum (l - H),  V = sum var:            z_fit = D / sqrt(V); large: the readings are less
+                                                likely than the model itself expects
+      u = sum g_x,  Ixx = sum h_x:              the score and information of a shift x -> x + delta
+                                                of the sensor's received level
+    fitted=False takes u* = u, I* = Ixx: exact under the model at the true (S, C) -- D has mean 0
+    and variance V, u mean 0 and variance Ixx, for any number of readings.  This is the form for
+    held-out readings: after solve_readings(holdout=...),
+    check_fit(res.obs_holdout, res.S, res.C, fitted=False) (that packing shares obs.perm).
+    fitted=True (default; S was fitted to these readings) removes what the fit of the pixel's own
+    s absorbs: u* = u - v^T J^-1 g, I* = Ixx - v^T J^-1 v, with J the expected information block of
+    s (qmc.confidence's, plus ridge I), v the cross information and g the S-gradient at S -- Neyman's
+    C(alpha) statistic, valid to first order even where S is not exactly the conditional MLE.
+    z_shift = -u* / sqrt(I*) (positive: the sensor reads high) and shift = -u* / I* is the
+    one-step estimate of delta in model-domain units.  D is NOT corrected for the fit: on the
+    fitted readings z_fit is biased low by about R / 2 in D; held-out readings with fitted=False
+    give the exact form.  C is treated as known, as in qmc.confidence.  `ridge` is the ridge the
+    fit of S carried (solve(check=True) passes default_confidence_ridge).
+    flags (bits): 1 untestable -- fitted and J is not positive definite or I* <= 1e-4 Ixx (the
+    shift is confounded with s: fewer readings than R, say; u*, I* are 0); 2 invalid -- log model
+    and a reading with T_hat + offset <= 0 (all four statistics 0); 4 saturated -- a reading whose
+    P underflows (it enters l as -log FLT_MIN and adds 0 to the score).  Nothing is ever NaN.
+    Under the log model a shift of x = log(T_hat + offset) is a common gain on the pixel's s but
+    for the offset: with fitted=True and ridge = 0 it is confounded with the fit and every pixel is
+    untestable; the ridge of the fit, or held-out readings with fitted=False, make the test live.
+    Returns CheckResult(n, z_fit, z_shift, shift, flags, D, V, u, info (each (I, J)), untestable,
+    invalid, saturated (counts), z_fit_total = sum D / sqrt(sum V) over the valid pixels); its
+    .flagged(alpha, which) is the Bonferroni mask.  To re-solve without the flagged sensors:
+      keep = ~r.flagged(0.01, "either")
+      obs2 = Observations(Y, Wx * keep, ...)      # or filter the readings by keep[i, j] and re-pack
+    obs: the Observations; S (R,1,I,J) or (R,P), C (R,K).  Raises ValueError for
+    obs.loss == "squared", ridge < 0 or shapes that do not match obs, before any GPU call."""
+    check_check_fit(getattr(obs, "loss", None), ridge)
+    R = S.shape[0]
+    if S.numel() != R * obs.P or tuple(C.shape) != (R, obs.K):
+        raise ValueError("check_fit needs S (R,1,I,J) or (R,P) and C (R,K) of obs's shape "
+                         "(P = %d, K = %d), got %s and %s"
+                         % (obs.P, obs.K, tuple(S.shape), tuple(C.shape)))
+    S_pos, Cd = _inputs(obs, S, C, R)
+    stat, count, flags = _check_pos(obs, S_pos, Cd, R, bool(fitted), ridge)
+    ip = obs.iperm().long()
+    st = stat[ip].reshape(obs.I, obs.J, 4)
+    return check_result(st[..., 0].contiguous(), st[..., 1].contiguous(), st[..., 2].contiguous(),
+                        st[..., 3].contiguous(), count[ip].reshape(obs.I, obs.J),
+                        flags[ip].reshape(obs.I, obs.J))
 
 
 @dataclass
@@ -793,14 +948,16 @@ def fit_S_smooth(obs, C, smooth, smooth_kind="quad", smooth_delta=None, S_init=N
 
 @dataclass
 class PostSolve:
-    """solve()'s validated post-solve options (check_post_solve): the four counts, 0 = off, and
-    the confidence kind (None = off) with its ridge (None = default_confidence_ridge)."""
+    """solve()'s validated post-solve options (check_post_solve): the four counts, 0 = off, the
+    confidence kind (None = off) with its ridge (None = default_confidence_ridge), and whether
+    check_fit runs."""
     polish_c: int = 0
     polish_s: int = 0
     polish_smooth: int = 0
     calibrate: int = 0
     confidence: Optional[str] = None
     confidence_ridge: Optional[float] = None
+    check: bool = False
 
 
 def _check_option(name, value, generator, loss):
@@ -825,9 +982,9 @@ def check_polish_c(polish_c, generator, loss):
 
 
 def check_post_solve(generator, loss, smooth, polish_s=0, polish_c=0, polish_smooth=0, calibrate=0,
-                     confidence=None, confidence_ridge=None):
+                     confidence=None, confidence_ridge=None, check=False):
     """Validate solve(polish_s=, polish_c=, polish_smooth=, calibrate=, confidence=,
-    confidence_ridge=) (before anything touches a device) -> PostSolve.  `smooth` is solve's
+    confidence_ridge=, check=) (before anything touches a device) -> PostSolve.  `smooth` is solve's
     checked weight of the smoothness prior."""
     n_s = _check_option("polish_s", polish_s, generator, loss)
     if n_s and smooth > 0.0:
@@ -841,8 +998,9 @@ def check_post_solve(generator, loss, smooth, polish_s=0, polish_c=0, polish_smo
     n_cal = _check_option("calibrate", calibrate, generator, loss)
     if _check_option("confidence", confidence is not None, generator, loss):
         check_confidence(confidence, confidence_ridge, loss)
+    do_check = bool(_check_option("check", bool(check), generator, loss))
     return PostSolve(polish_c=n_c, polish_s=n_s, polish_smooth=n_smooth, calibrate=n_cal,
-                     confidence=confidence, confidence_ridge=confidence_ridge)
+                     confidence=confidence, confidence_ridge=confidence_ridge, check=do_check)
 
 
 def post_solve(res, obs, opts, lambda_s, lambda_c, project_s, smooth, smooth_kind, smooth_delta):
@@ -856,6 +1014,8 @@ def post_solve(res, obs, opts, lambda_s, lambda_c, project_s, smooth, smooth_kin
                      (without S, C); what follows runs on its .obs, the calibrated model
       confidence     res.std_S and res.unidentified at the returned S, C, the ridge
                      opts.confidence_ridge or lambda_s / ||S||_F
+      check          res.check = check_fit at the returned S, C, fitted, the ridge
+                     lambda_s / ||S||_F
     opts: check_post_solve's PostSolve; a step that is off is skipped.  -> res."""
     if opts.polish_c:
         r = fit_C(obs, res.S, C_init=res.C, ridge=default_confidence_ridge(res.C, lambda_c),
@@ -885,4 +1045,7 @@ def post_solve(res, obs, opts, lambda_s, lambda_c, project_s, smooth, smooth_kin
                  else float(opts.confidence_ridge))
         c = confidence(obs, res.S, res.C, kind=opts.confidence, ridge=ridge)
         res.std_S, res.unidentified = c.std_S, c.unidentified
+    if opts.check:
+        res.check = check_fit(obs, res.S, res.C, fitted=True,
+                              ridge=default_confidence_ridge(res.S, lambda_s))
     return res

@@ -24,10 +24,11 @@ from . import _lib
 from ._model import _dev, map_nmse
 # the post-solve estimators live in fits.py; qmc.fit_S etc. stay the user-facing spellings
 from .fits import (  # noqa: F401
-    DESIGN_CRITERIA, INFO_KINDS, CalibrateResult, ConfidenceResult, DesignResult, FitCResult,
+    DESIGN_CRITERIA, INFO_KINDS, CalibrateResult, CheckResult, ConfidenceResult, DesignResult,
+    FitCResult,
     FitNoiseResult, FitSResult, FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos,
     _fit_s_smooth_pos, _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_design,
-    check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
+    check_fit, check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
     design, fit_C, fit_noise,
     fit_S, fit_S_smooth, model_nll, post_solve, shifted_boundaries)
 from .fused import PassEngine, check_smooth
@@ -57,6 +58,7 @@ class SolveResult:
     polish_smooth: Optional["FitSSmoothResult"] = None
     # solve(calibrate=n): the qmc.calibrate run on S, C (without them; .obs is the calibrated one)
     calibration: Optional["CalibrateResult"] = None
+    check: Optional["CheckResult"] = None  # solve(check=True): qmc.check_fit at the returned S, C
 
 
 class FreeSSolver(AlternatingSolver):
@@ -250,7 +252,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
           project_s=None, holdout=0.0, check_every=10, patience=5, holdout_seed=0,
           smooth=0.0, smooth_kind="quad", smooth_delta=None, confidence=None,
           confidence_ridge=None, polish_s=0, polish_c=0, polish_smooth=0, obs_holdout=None,
-          calibrate=0):
+          calibrate=0, check=False):
     """Alternating S/C probit-MLE (qmc/qmc.ipynb :559-645).
 
     Args mirror the notebook globals: Y (K,1,I,J) bin indices, Wx (K,1,I,J) 0/1 mask,
@@ -326,6 +328,11 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     is the CalibrateResult (without S, C; its .obs carries the calibrated model).  Raises
     ValueError with a generator and with loss="squared".  The default 0 leaves every path and
     result bit-identical.
+    check=True (free S and holdout solves; not in the reference): last of all, on the calibrated
+    observations if calibrate= ran, result.check = qmc.check_fit(obs, S, C, fitted=True) with the
+    ridge lambda_s / ||S||_F: per-pixel goodness of fit and level-shift score tests of the readings
+    the solve ran on.  Raises ValueError with a generator and with loss="squared".  The default
+    False leaves every path and result as it is.
     obs= gives the packed observations (an Observations, e.g. Observations.from_readings for a
     list of sensor reports); Y and Wx may then be None, and K, I, J, the model and the loss are
     obs's.  obs_holdout= (with obs=, free S only) is a second Observations packed with obs.perm and
@@ -354,7 +361,7 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     post = check_post_solve(generator, obs.loss if obs is not None else loss, smooth,
                             polish_s=polish_s, polish_c=polish_c, polish_smooth=polish_smooth,
                             calibrate=calibrate, confidence=confidence,
-                            confidence_ridge=confidence_ridge)
+                            confidence_ridge=confidence_ridge, check=check)
     if log_model and obs is None:
         # the reference log model's default offset (qmc/quantization_model_log.py:7, 9)
         offset = LOG_OFFSET if offset is None else float(offset)

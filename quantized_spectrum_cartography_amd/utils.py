@@ -117,6 +117,33 @@ def entry_information(T_hat, Y, bin_boundaries, noise_std, offset=0.0, log_model
     return H if T_hat.is_cuda else H.to(T_hat.device)
 
 
+def entry_check(Y, T, obs_or_model):
+    """Elementwise terms of qmc.check_fit at the map values T and codes Y -- the HIP op
+    qsc_entry_check (the device function of the check's walk; formulas in include/qsc.h):
+    l - H (the entry's -log P minus its expectation under the model), var (the variance of l),
+    g_x (the score in the model domain x at the code Y; 0 where P underflows), h_x (the Fisher
+    information in x) and dxdt (1, or 1 / (T + offset) under the log model).
+
+    obs_or_model: an Observations (its model is used) or a qsc_model from _lib.make_model.
+    Returns a float32 tensor (5, *T.shape) on T's device; under the log model an element with
+    T + offset <= 0 gets five zeros."""
+    from . import _lib
+    from ._model import _dev
+    m = getattr(obs_or_model, "model", obs_or_model)
+    if not isinstance(m, _lib.QscModel):
+        raise ValueError("obs_or_model must be an Observations or a qsc_model")
+    if m.loss == _lib.LOSSES["squared"]:
+        raise ValueError('loss="squared" is not a likelihood: there is no model to check')
+    Td = _dev(T.detach().to(torch.float32))
+    Yd = _dev(Y.to(torch.int64))
+    Yd, Td = torch.broadcast_tensors(Yd, Td)
+    Yd, Td = Yd.contiguous(), Td.contiguous()
+    out = torch.empty((5,) + tuple(Td.shape), dtype=torch.float32, device=Td.device)
+    _lib.call("qsc_entry_check", _lib.ptr(Yd), _lib.ptr(Td), Td.numel(), m, _lib.ptr(out),
+              _lib.stream())
+    return out if T.is_cuda else out.to(T.device)
+
+
 def entry_calibration(Y, T, obs_or_model, tau=0.0, beta=0.0, kind="expected"):
     """Elementwise terms of qmc.fit_noise at the map values T and codes Y: the per-entry
     f = -log P, its gradient (g_tau, g_beta) and curvature (H_tt, H_tb, H_bb) in the log noise
