@@ -422,8 +422,6 @@ inline bool cfit_layout_ok(const qsc_obs_desc* d, const qsc_model* m, int R) {
   return true;
 }
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 int cfit_walk(const qsc_obs_desc* d, const void* c_entries, const int32_t* c_width,
               const int64_t* c_off, const int32_t* c_kmap, const qsc_model* m, int R, int RP, int G,
               const float* S, int kind, const CfitWs& w, hipStream_t hs) {

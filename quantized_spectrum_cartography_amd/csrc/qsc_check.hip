@@ -28,8 +28,6 @@
 // marks the position).  No workspace, no atomics: two calls agree bit for bit.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "qsc_common.cuh"
 #include "qsc_newton.cuh"
 
@@ -106,54 +104,30 @@ __global__ void __launch_bounds__(kBlock) scheck_kernel(
     for (int i = 0; i < NV; ++i) g[i] = v[i] = 0.0f;
 #pragma unroll
     for (int i = 0; i < NT; ++i) Jt[i] = 0.0f;
-    const int nch = width[s] >> 2;  // 4-entry chunks of every list of the slice
-    const int64_t base = off[s] + l * 4 + 2 * h;
-    uint32_t n0, n1;
-    load_pair<E>(ent, base, n_ent, pad_value, n0, n1);
-    for (int ch = 0; ch < nch; ++ch) {
-      const uint32_t w[2] = {n0, n1};
-      // the next chunk's entries while this one is worked (clamped in load_pair)
-      load_pair<E>(ent, base + (int64_t)(ch + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0, n1);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        int k, code;
-        bool pad;
-        decode<E, SR>(w[e], K, Ko, lk.nbins, k, code, pad);
-        float cv[RP];
-        QSC_ROW_LOAD(RP, cv, Cl + k * CP)
-        float t = 0.0f;
-#pragma unroll
-        for (int r = 0; r < RP; ++r) t = __builtin_fmaf(sv[r], cv[r], t);
-        float dl, var, gx, hx, dxdt;
-        bool sat, neg;
-        entry_check<LOGIT, LOG>(t, code, El, lk, dl, var, gx, hx, dxdt, sat, neg);
-        // a pad and an entry with t + offset <= 0 add exactly 0 (selects: their terms may be NaN)
-        const bool on = live && !pad && !neg;
-        inv = inv || (live && !pad && neg);
-        satf = satf || (on && sat);
-        n += on ? 1 : 0;
-        D += on ? (double)dl : 0.0;
-        V += on ? (double)var : 0.0;
-        const float gu = (on && !sat) ? gx : 0.0f;
-        const float hu = on ? hx : 0.0f;
-        u += gu;
-        Ixx += hu;
-        if (FITTED) {
-          const float dx = on ? dxdt : 0.0f;
-          const float ge = gu * dx, hv = hu * dx;
-          const float hj = hv * dx;
-#pragma unroll
-          for (int i = 0; i < NV; ++i) {
-            g[i] = __builtin_fmaf(ge, cv[i], g[i]);
-            v[i] = __builtin_fmaf(hv, cv[i], v[i]);
-            const float hi_ = hj * cv[i];
-#pragma unroll
-            for (int j = i; j < NV; ++j)
-              Jt[tri<RP>(i, j)] = __builtin_fmaf(hi_, cv[j], Jt[tri<RP>(i, j)]);
-          }
-        }
+    QSC_SLICE_LISTS(s);
+    QSC_WALK_BEGIN(RP, CP, E, SR, sv)
+      float dl, var, gx, hx, dxdt;
+      bool sat, neg;
+      entry_check<LOGIT, LOG>(t, code, El, lk, dl, var, gx, hx, dxdt, sat, neg);
+      // a pad and an entry with t + offset <= 0 add exactly 0 (selects: their terms may be NaN)
+      const bool on = live && !pad && !neg;
+      inv = inv || (live && !pad && neg);
+      satf = satf || (on && sat);
+      n += on ? 1 : 0;
+      D += on ? (double)dl : 0.0;
+      V += on ? (double)var : 0.0;
+      const float gu = (on && !sat) ? gx : 0.0f;
+      const float hu = on ? hx : 0.0f;
+      u += gu;
+      Ixx += hu;
+      if (FITTED) {
+        const float dx = on ? dxdt : 0.0f;
+        const float ge = gu * dx, hv = hu * dx;
+        const float hj = hv * dx;
+        QSC_BLOCK_UPDATE(RP, NV, Jt, hj, cv, g[i_] = __builtin_fmaf(ge, cv[i_], g[i_]);
+                         v[i_] = __builtin_fmaf(hv, cv[i_], v[i_]);)
       }
-    }
+    QSC_WALK_END
     // the two halves' partial sums: the same bits on both lanes from here on
     D += __shfl_xor(D, 32, 64);
     V += __shfl_xor(V, 32, 64);
@@ -240,13 +214,8 @@ __global__ void __launch_bounds__(kBlock) entry_check_kernel(const int64_t* __re
                                                              const float* __restrict__ T,
                                                              int64_t n, Link lk, Edges E_,
                                                              float* __restrict__ out) {
-  __shared__ float2 se[QSC_MAX_BOUNDS - 1];
-  for (int i = threadIdx.x; i < lk.nbins; i += blockDim.x) se[i] = E_.e[i];
-  __syncthreads();
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t y = Y[i];
-    y = y < 0 ? 0 : (y >= lk.nbins ? lk.nbins - 1 : y);
+  QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);
+  QSC_ENTRYWISE_BEGIN(lk)
     float dl, var, gx, hx, dxdt;
     bool sat, neg;
     entry_check<LOGIT, LOG>(T[i], (int)y, se, lk, dl, var, gx, hx, dxdt, sat, neg);
@@ -255,12 +224,10 @@ __global__ void __launch_bounds__(kBlock) entry_check_kernel(const int64_t* __re
     out[2 * n + i] = neg ? 0.0f : gx;
     out[3 * n + i] = neg ? 0.0f : hx;
     out[4 * n + i] = neg ? 0.0f : dxdt;
-  }
+  QSC_ENTRYWISE_END
 }
 
 }  // namespace
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 
@@ -273,21 +240,18 @@ QSC_API int qsc_scheck(const qsc_obs_desc* d, const void* s_entries, const int32
     return QSC_EINVAL;
   if ((fitted != 0 && fitted != 1) || !(ridge >= 0.0f)) return QSC_EINVAL;
   if (!info_layout_ok(d, m, R) || (d->s_entries > 0 && !s_entries)) return QSC_EINVAL;
-  const int RP = qsc_rank_pad(R);
-  const size_t shm = sinfo_lds(d->K, RP, d->nbins);
-  if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
-  const Link lk = make_link(m);
-  Edges E;
-  make_edges(m, &E);
-  const int nslices = d->Pp / QSC_SLICE;
-  const dim3 grid((unsigned)slice_grid(nslices, 8)), blk(kBlock);
+  WalkLaunch wl;
+  const int rc = walk_launch(d, m, R, &wl);
+  if (rc != QSC_OK) return rc;
+  const int RP = wl.RP;
+  const dim3 grid((unsigned)slice_grid(wl.nslices, 8)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   const int kind = INFO_EXPECTED;  // (h_x is the expected information: the kind is fixed)
-#define SCHECK_LAUNCH_(RPV, ET, SRV, LGT, LOGV, FT)                                              \
-  hipLaunchKernelGGL((scheck_kernel<RPV, ET, SRV, LGT, LOGV, FT>), grid, blk, shm, hs,           \
-                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
-                     R, d->K, d->P, perm, S, C, ridge, reinterpret_cast<float4*>(stat), count,   \
-                     flags)
+#define SCHECK_LAUNCH_(RPV, ET, SRV, LGT, LOGV, FT)                                           \
+  hipLaunchKernelGGL((scheck_kernel<RPV, ET, SRV, LGT, LOGV, FT>), grid, blk, wl.shm, hs,     \
+                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, wl.nslices, \
+                     wl.lk, wl.E, R, d->K, d->P, perm, S, C, ridge,                           \
+                     reinterpret_cast<float4*>(stat), count, flags)
 #define SCHECK_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                     \
   do {                                                                 \
     if (fitted) SCHECK_LAUNCH_(RPV, ET, SRV, LGT, LOGV, true);         \
@@ -302,13 +266,12 @@ QSC_API int qsc_scheck(const qsc_obs_desc* d, const void* s_entries, const int32
 
 QSC_API int qsc_entry_check(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
                             float* out, void* stream) {
-  if (!info_model_ok(m) || n < 0 || (n > 0 && (!Y || !T || !out))) return QSC_EINVAL;
+  if (!entry_args_ok(m, n, Y, T, out)) return QSC_EINVAL;
   if (n == 0) return QSC_OK;
   const Link lk = make_link(m);
   Edges E;
   make_edges(m, &E);
-  const int64_t want = ceil_div(n, kBlock);
-  const dim3 grid((unsigned)std::min<int64_t>(want, 8192)), blk(kBlock);
+  const dim3 grid = entry_grid(n), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   const int kind = INFO_EXPECTED;
 #define ENTRY_LAUNCH(LGT, LOGV, KD) \

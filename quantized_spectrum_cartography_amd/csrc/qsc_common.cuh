@@ -25,6 +25,9 @@
     if (e__ != hipSuccess) return (int)e__;         \
   } while (0)
 
+// the C ABI's `void* stream` as the runtime's handle
+#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+
 namespace qsc {
 
 // Derived per-call constants of the probit model, passed by value to kernels.

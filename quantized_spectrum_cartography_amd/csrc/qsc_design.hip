@@ -36,10 +36,6 @@ using namespace qsc;
 
 enum { DESIGN_D = QSC_DESIGN_D, DESIGN_A = QSC_DESIGN_A, DESIGN_V = QSC_DESIGN_V };
 
-inline size_t sgain_lds(int K, int RP, int nbins) {
-  return sinfo_lds(K, RP, nbins) + (size_t)K * 4;
-}
-
 template <int RP, bool LOGIT, bool LOG, int CRIT>
 __global__ void __launch_bounds__(kBlock) sgain_kernel(
     int nslices, Link lk, Edges E_, int R, int K, int P_, const int* __restrict__ perm,
@@ -52,8 +48,7 @@ __global__ void __launch_bounds__(kBlock) sgain_kernel(
   float* wl = reinterpret_cast<float*>(El + lk.nbins);  // [K], ones without a plan
   for (int k = threadIdx.x; k < K; k += kBlock) wl[k] = w != nullptr ? w[k] : 1.0f;
   __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int l = lane & (QSC_SLICE - 1), h = lane >> 5;
+  QSC_SLANE_GEOMETRY();
   int cnt_first = 0, cnt_bad = 0;  // (wave-uniform)
   for (int s = blockIdx.x * kWaves + wave; s < nslices; s += gridDim.x * kWaves) {
     const int64_t q = (int64_t)s * QSC_SLICE + l;
@@ -76,13 +71,7 @@ __global__ void __launch_bounds__(kBlock) sgain_kernel(
         float hh = entry_curvature<LOGIT, LOG, INFO_EXPECTED>(t, 0, El, lk);
         if (LOG) hh = (t + lk.offset > 0.0f) ? hh : 0.0f;
         hh *= wk;
-#pragma unroll
-        for (int i = 0; i < RP; ++i) {
-          const float hi_ = hh * cv[i];
-#pragma unroll
-          for (int j = i; j < RP; ++j)
-            acc[tri<RP>(i, j)] = __builtin_fmaf(hi_, cv[j], acc[tri<RP>(i, j)]);
-        }
+        QSC_BLOCK_UPDATE(RP, RP, acc, hh, cv, )
       }
     }
     // the two halves' parts (the same bits on both lanes)
@@ -167,8 +156,6 @@ __global__ void __launch_bounds__(kBlock) sgain_kernel(
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API int qsc_sgain(const float* S, const float* C, const float* J, const int32_t* perm,
@@ -182,32 +169,23 @@ QSC_API int qsc_sgain(const float* S, const float* C, const float* J, const int3
     return QSC_EINVAL;
   if (criterion != DESIGN_D && criterion != DESIGN_A && criterion != DESIGN_V) return QSC_EINVAL;
   if (criterion == DESIGN_V && !G) return QSC_EINVAL;
-  const int RP = qsc_rank_pad(R);
-  const int nbins = m->nbounds - 1;
-  const size_t shm = sgain_lds(K, RP, nbins);
-  if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
-  const Link lk = make_link(m);
-  Edges E;
-  make_edges(m, &E);
-  const int nslices = Pp / QSC_SLICE;
-  const dim3 grid((unsigned)slice_grid(nslices, 8)), blk(kBlock);
+  WalkLaunch wl;
+  const int rc = walk_launch(K, Pp, m, R, (size_t)K * 4, &wl);  // (w[K] after the edges)
+  if (rc != QSC_OK) return rc;
+  const int RP = wl.RP;
+  const dim3 grid((unsigned)slice_grid(wl.nslices, 8)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   const int kind = INFO_EXPECTED;  // (the planned readings' codes are not known: always expected)
-#define SGAIN_LAUNCH_(RPV, LGT, LOGV, CR)                                                        \
-  hipLaunchKernelGGL((sgain_kernel<RPV, LGT, LOGV, CR>), grid, blk, shm, hs, nslices, lk, E, R, K, \
-                     P, perm, S, C, J, w, G, ridge, gain, n_first, n_bad)
+#define SGAIN_LAUNCH_(RPV, LGT, LOGV, CR)                                                  \
+  hipLaunchKernelGGL((sgain_kernel<RPV, LGT, LOGV, CR>), grid, blk, wl.shm, hs, wl.nslices, \
+                     wl.lk, wl.E, R, K, P, perm, S, C, J, w, G, ridge, gain, n_first, n_bad)
 #define SGAIN_CRIT_(RPV, LGT, LOGV)                                       \
   do {                                                                    \
     if (criterion == DESIGN_D) SGAIN_LAUNCH_(RPV, LGT, LOGV, DESIGN_D);   \
     else if (criterion == DESIGN_A) SGAIN_LAUNCH_(RPV, LGT, LOGV, DESIGN_A); \
     else SGAIN_LAUNCH_(RPV, LGT, LOGV, DESIGN_V);                         \
   } while (0)
-#define SGAIN_LAUNCH(LGT, LOGV, KD)                 \
-  do {                                              \
-    if (RP == 4) SGAIN_CRIT_(4, LGT, LOGV);         \
-    else if (RP == 8) SGAIN_CRIT_(8, LGT, LOGV);    \
-    else SGAIN_CRIT_(16, LGT, LOGV);                \
-  } while (0)
+#define SGAIN_LAUNCH(LGT, LOGV, KD) QSC_RP_DISPATCH(SGAIN_CRIT_, LGT, LOGV)
   QSC_INFO_DISPATCH(SGAIN_LAUNCH);
 #undef SGAIN_LAUNCH
 #undef SGAIN_CRIT_

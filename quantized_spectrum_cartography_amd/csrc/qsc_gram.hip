@@ -139,8 +139,6 @@ __global__ void __launch_bounds__(256) chol_solve_kernel(const float* __restrict
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API size_t qsc_gram_workspace_bytes(int32_t R, int32_t P, int32_t K) {

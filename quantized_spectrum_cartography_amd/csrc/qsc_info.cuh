@@ -1,6 +1,6 @@
 // qsc_info.cuh — the link terms (P, P', P''), the per-entry curvature and terms, the S-format list
 // decode and the dispatch macros shared by qsc_info.hip (information blocks) and, through
-// qsc_newton.cuh, the Newton fits (qsc_sfit.hip, qsc_cfit.hip, qsc_sfit_smooth.hip).
+// qsc_newton.cuh, every other kernel over the packed lists (that header names them).
 // qsc_info.hip's header has the formulas and the numerics.
 //
 // Everything lives in an anonymous namespace on purpose: each translation unit gets its own
@@ -428,19 +428,22 @@ inline bool info_layout_ok(const qsc_obs_desc* d, const qsc_model* m, int R) {
 // ... for LAUNCH(LOGIT, LOG, KIND)
 #define QSC_INFO_DISPATCH(LAUNCH) QSC_INFO_DISPATCH_(QSC_INFO_APPLY_, LAUNCH)
 
-// ... and over the layout for LAUNCH(RP, E, SR, LOGIT, LOG, KIND): rank pad 4 / 8 / 16, narrow /
-// wide / signed-row entries (signed rows: linear one-bit only); reads RP and d as well
-#define QSC_LAYOUT_E_(LAUNCH, RPV, LGT, LOGV, KD)                    \
+// dispatch over the rank pad 4 / 8 / 16 for LAUNCH(RP, the further arguments); reads RP
+#define QSC_RP_DISPATCH(LAUNCH, ...)              \
+  do {                                            \
+    if (RP == 4) LAUNCH(4, ##__VA_ARGS__);        \
+    else if (RP == 8) LAUNCH(8, ##__VA_ARGS__);   \
+    else LAUNCH(16, ##__VA_ARGS__);               \
+  } while (0)
+
+// ... and over the layout for LAUNCH(RP, E, SR, LOGIT, LOG, KIND): the rank pad, narrow / wide /
+// signed-row entries (signed rows: linear one-bit only); reads RP and d as well
+#define QSC_LAYOUT_E_(RPV, LAUNCH, LGT, LOGV, KD)                    \
   do {                                                               \
     if (d->rowfmt == 1) {                                            \
       if (!LOGV) LAUNCH(RPV, uint16_t, true, LGT, false, KD);        \
     } else if (d->wide) LAUNCH(RPV, uint32_t, false, LGT, LOGV, KD); \
     else LAUNCH(RPV, uint16_t, false, LGT, LOGV, KD);                \
   } while (0)
-#define QSC_LAYOUT_RP_(LAUNCH, LGT, LOGV, KD)                    \
-  do {                                                           \
-    if (RP == 4) QSC_LAYOUT_E_(LAUNCH, 4, LGT, LOGV, KD);        \
-    else if (RP == 8) QSC_LAYOUT_E_(LAUNCH, 8, LGT, LOGV, KD);   \
-    else QSC_LAYOUT_E_(LAUNCH, 16, LGT, LOGV, KD);               \
-  } while (0)
+#define QSC_LAYOUT_RP_(LAUNCH, LGT, LOGV, KD) QSC_RP_DISPATCH(QSC_LAYOUT_E_, LAUNCH, LGT, LOGV, KD)
 #define QSC_LAYOUT_DISPATCH(LAUNCH) QSC_INFO_DISPATCH_(QSC_LAYOUT_RP_, LAUNCH)

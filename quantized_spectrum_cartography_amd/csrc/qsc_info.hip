@@ -32,8 +32,6 @@
 // inverse in place (QSC_CHOL_INVERSE); std_S from its column norms, std_T[k] = |L^-1 c_k|.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "qsc_common.cuh"
 #include "qsc_newton.cuh"
 
@@ -56,36 +54,12 @@ __global__ void __launch_bounds__(kBlock) sinfo_kernel(
     float acc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i] = 0.0f;
-    const int nch = width[s] >> 2;  // 4-entry chunks of every list of the slice
-    const int64_t base = off[s] + l * 4 + 2 * h;
-    uint32_t n0, n1;
-    load_pair<E>(ent, base, n_ent, pad_value, n0, n1);
-    for (int ch = 0; ch < nch; ++ch) {
-      const uint32_t v[2] = {n0, n1};
-      // the next chunk's entries while this one is worked (past the last list: the next slice's
-      // entries or the array's pad tail, QSC_ENTRY_TAIL; clamped in load_pair either way)
-      load_pair<E>(ent, base + (int64_t)(ch + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0, n1);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        int k, code;
-        bool pad;
-        decode<E, SR>(v[e], K, Ko, lk.nbins, k, code, pad);
-        float cv[RP];
-        QSC_ROW_LOAD(RP, cv, Cl + k * CP)
-        float t = 0.0f;
-#pragma unroll
-        for (int r = 0; r < RP; ++r) t = __builtin_fmaf(sv[r], cv[r], t);
-        float hh = entry_curvature<LOGIT, LOG, KIND>(t, code, El, lk);
-        hh = pad ? 0.0f : hh;  // a pad adds exactly 0 (c_k is finite)
-#pragma unroll
-        for (int i = 0; i < RP; ++i) {
-          const float hi_ = hh * cv[i];
-#pragma unroll
-          for (int j = i; j < RP; ++j)
-            acc[tri<RP>(i, j)] = __builtin_fmaf(hi_, cv[j], acc[tri<RP>(i, j)]);
-        }
-      }
-    }
+    QSC_SLICE_LISTS(s);
+    QSC_WALK_BEGIN(RP, CP, E, SR, sv)
+      float hh = entry_curvature<LOGIT, LOG, KIND>(t, code, El, lk);
+      hh = pad ? 0.0f : hh;  // a pad adds exactly 0 (c_k is finite)
+      QSC_BLOCK_UPDATE(RP, RP, acc, hh, cv, )
+    QSC_WALK_END
     // the two halves' partial blocks (the same bits on both lanes), then each half's rows
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i] += __shfl_xor(acc[i], 32, 64);
@@ -112,15 +86,10 @@ __global__ void __launch_bounds__(kBlock) entry_info_kernel(const int64_t* __res
                                                             const float* __restrict__ T, int64_t n,
                                                             Link lk, Edges E_,
                                                             float* __restrict__ H) {
-  __shared__ float2 se[QSC_MAX_BOUNDS - 1];
-  for (int i = threadIdx.x; i < lk.nbins; i += blockDim.x) se[i] = E_.e[i];
-  __syncthreads();
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t y = Y[i];
-    y = y < 0 ? 0 : (y >= lk.nbins ? lk.nbins - 1 : y);
+  QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);
+  QSC_ENTRYWISE_BEGIN(lk)
     H[i] = entry_curvature<LOGIT, LOG, KIND>(T[i], (int)y, se, lk);
-  }
+  QSC_ENTRYWISE_END
 }
 
 // One thread per position: Cholesky of J_q + ridge I (rows >= R replaced by the identity), the
@@ -194,8 +163,6 @@ __global__ void __launch_bounds__(kBlock) info_std_kernel(
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
@@ -204,19 +171,16 @@ QSC_API int qsc_sinfo(const qsc_obs_desc* d, const void* s_entries, const int32_
   if (!d || !s_width || !s_off || !S || !C || !J || !info_model_ok(m)) return QSC_EINVAL;
   if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
   if (!info_layout_ok(d, m, R) || (d->s_entries > 0 && !s_entries)) return QSC_EINVAL;
-  const int RP = qsc_rank_pad(R);
-  const size_t shm = sinfo_lds(d->K, RP, d->nbins);
-  if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
-  const Link lk = make_link(m);
-  Edges E;
-  make_edges(m, &E);
-  const int nslices = d->Pp / QSC_SLICE;
-  const dim3 grid((unsigned)slice_grid(nslices, 8)), blk(kBlock);
+  WalkLaunch wl;
+  const int rc = walk_launch(d, m, R, &wl);
+  if (rc != QSC_OK) return rc;
+  const int RP = wl.RP;
+  const dim3 grid((unsigned)slice_grid(wl.nslices, 8)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
-#define SINFO_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                \
-  hipLaunchKernelGGL((sinfo_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,            \
-                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
-                     R, d->K, S, C, J)
+#define SINFO_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                             \
+  hipLaunchKernelGGL((sinfo_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, wl.shm, hs,      \
+                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, wl.nslices, \
+                     wl.lk, wl.E, R, d->K, S, C, J)
   QSC_LAYOUT_DISPATCH(SINFO_LAUNCH);
 #undef SINFO_LAUNCH
   QSC_CHECK_LAUNCH();
@@ -231,29 +195,24 @@ QSC_API int qsc_info_std(const float* J, const int32_t* perm, int32_t R, int32_t
     return QSC_EINVAL;
   const int RP = qsc_rank_pad(R);
   const dim3 grid((unsigned)ceil_div(Pp, kBlock)), blk(kBlock);
-  if (RP == 4)
-    hipLaunchKernelGGL(info_std_kernel<4>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
-                       ridge, std_S, std_T, nbad);
-  else if (RP == 8)
-    hipLaunchKernelGGL(info_std_kernel<8>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
-                       ridge, std_S, std_T, nbad);
-  else
-    hipLaunchKernelGGL(info_std_kernel<16>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K,
-                       ridge, std_S, std_T, nbad);
+#define STD_LAUNCH(RPV)                                                                          \
+  hipLaunchKernelGGL(info_std_kernel<RPV>, grid, blk, 0, STREAM(stream), J, perm, R, P, Pp, C, K, \
+                     ridge, std_S, std_T, nbad)
+  QSC_RP_DISPATCH(STD_LAUNCH);
+#undef STD_LAUNCH
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }
 
 QSC_API int qsc_entry_info(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
                            int32_t kind, float* H, void* stream) {
-  if (!info_model_ok(m) || n < 0 || (n > 0 && (!Y || !T || !H))) return QSC_EINVAL;
+  if (!entry_args_ok(m, n, Y, T, H)) return QSC_EINVAL;
   if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
   if (n == 0) return QSC_OK;
   const Link lk = make_link(m);
   Edges E;
   make_edges(m, &E);
-  const int64_t want = ceil_div(n, kBlock);
-  const dim3 grid((unsigned)std::min<int64_t>(want, 8192)), blk(kBlock);
+  const dim3 grid = entry_grid(n), blk(kBlock);
   hipStream_t hs = STREAM(stream);
 #define ENTRY_LAUNCH(LGT, LOGV, KD) \
   hipLaunchKernelGGL((entry_info_kernel<LGT, LOGV, KD>), grid, blk, 0, hs, Y, T, n, lk, E, H)

@@ -98,8 +98,6 @@ __global__ void __launch_bounds__(kMapBlock) map_normalize_kernel(const float* _
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API size_t qsc_map_compose_workspace_bytes(int32_t R, int32_t I, int32_t J) {

@@ -1,7 +1,8 @@
-// qsc_newton.cuh — what the Newton-fit kernels share: qsc_sfit.hip (per-pixel fit of S),
-// qsc_sfit_smooth.hip (the same under the smoothness prior), qsc_cfit.hip (per-bin fit of C) and,
-// for the staging, the lane geometry and the factorisation, qsc_info.hip.  Each rule below is
-// stated here once; the tests pin every one of them to the bit.
+// qsc_newton.cuh — what the kernels over the packed lists share: the Newton fits qsc_sfit.hip
+// (per-pixel fit of S), qsc_sfit_smooth.hip (the same under the smoothness prior), qsc_cfit.hip
+// (per-bin fit of C) and qsc_qfit.hip (the model's own parameters), and the estimators that walk
+// the same lists or factor the same blocks: qsc_info.hip, qsc_check.hip, qsc_design.hip.  Each
+// rule below is stated here once; the tests pin every one of them to the bit.
 //
 // The objective.  One row x (a position's s, or a bin's c) minimises
 //     f(x) = sum_{entries} -log max(P(code | t = x . y), FLT_MIN) + ridge / 2 |x|^2
@@ -20,13 +21,21 @@
 // decrease below ~1e-6 is invisible, true Newton steps are rejected, and the iteration stops
 // |g| ~ sqrt(1e-6 lambda) short -- 1e-3 to 1e-2 relative at ridge 1e-2, measured.
 //
-// The S-format walk (QSC_WALK_SLICE; sinfo_kernel walks the same way).  One wave per slice of
-// QSC_SLICE positions, grid-stride over the slices, two lanes per position; lane half h takes
-// entries 2h, 2h + 1 of every 4-entry chunk in list order; C^T and the edges sit in LDS at the
-// info_pitch pitch; the next chunk's entries are loaded while this one is worked, with clamped
-// reads.  The halves are added once with a lane swap (a + b is the same bits on both lanes), so
+// The S-format walk (QSC_SLICE_LISTS, QSC_WALK_BEGIN ... QSC_WALK_END: sinfo_kernel,
+// scheck_kernel, qfit_walk_kernel and, through QSC_WALK_SLICE, sfit_kernel and
+// sfit_smooth_kernel).  One wave per slice of QSC_SLICE positions, grid-stride over the slices,
+// two lanes per position; lane half h takes entries 2h, 2h + 1 of every 4-entry chunk in list
+// order; C^T and the edges sit in LDS at the info_pitch pitch; the next chunk's entries are loaded
+// while this one is worked, with clamped reads.  Three things hold for every user: no read leaves
+// the entry array (load_pair); a pad entry adds exactly 0 to every sum (its terms are replaced
+// by 0 with a select, and the row it reads, row 0, is finite); the entry order, and with it every sum, is fixed by the packing
+// alone.  The halves are added once with a lane swap (a + b is the same bits on both lanes), so
 // from there on both lanes of a position hold the same state and take the same decisions.  No
-// floating-point atomics: the order of every sum is fixed by the packing alone.
+// floating-point atomics.
+//
+// The block update (QSC_BLOCK_UPDATE: sinfo_kernel, sgain_kernel, scheck_kernel and
+// QSC_ENTRY_ACCUMULATE).  J += h y y^T on the packed upper triangle: J[tri(i, j)] += (h y[i]) y[j],
+// i <= j, the product h y[i] rounded first, then one fma per element.
 //
 // The iteration, the same structure for every row:
 //     evaluate (f, g, J) at x = x_init;  mu = mu0
@@ -60,8 +69,9 @@
 // with functions the same arithmetic came out of the compiler with other register counts in 124
 // of the 255 kernels of the four files, twice at the cost of a wave of occupancy (DESIGN.md
 // section 7o).  A macro expands to the statements the kernels used to carry, so every kernel's
-// machine code is what its open-coded body gave (profiles/newton_shared/isa_compare.txt), and a
-// rule still has one home.  Each macro's comment lists what it declares in the caller's scope
+// machine code is what its open-coded body gave (profiles/newton_shared/isa_compare.txt and, for
+// the walk, the block update and the element-wise skeleton, profiles/walk_shared/), and a rule
+// still has one home.  Each macro's comment lists what it declares in the caller's scope
 // and what it reads from it; names ending in an underscore are the macros' own.
 #pragma once
 #include <algorithm>
@@ -101,6 +111,39 @@ inline size_t newton_ws_bytes(const qsc_obs_desc* d, int R) {
 inline bool newton_args_ok(int kind, float ridge, float mu0, float tol, int steps) {
   return (kind == INFO_EXPECTED || kind == INFO_OBSERVED) && ridge >= 0.0f && mu0 >= 0.0f &&
          tol > 0.0f && steps >= 1;
+}
+
+// what a launch of a walk over the slices takes besides its own arguments
+struct WalkLaunch {
+  int RP;
+  size_t shm;  // C^T, the edges and `extra_lds` bytes of the caller's own
+  Link lk;
+  Edges E;
+  int nslices;
+};
+// ... filled for K bins and Pp positions; QSC_EUNSUPPORTED when the tables do not fit the LDS.
+// The caller's last check: every argument is valid by then (m: info_model_ok).
+inline int walk_launch(int K, int Pp, const qsc_model* m, int R, size_t extra_lds, WalkLaunch* wl) {
+  wl->RP = qsc_rank_pad(R);
+  wl->shm = sinfo_lds(K, wl->RP, m->nbounds - 1) + extra_lds;
+  if (wl->shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
+  wl->lk = make_link(m);
+  make_edges(m, &wl->E);
+  wl->nslices = Pp / QSC_SLICE;
+  return QSC_OK;
+}
+// ... for a packed layout (info_layout_ok: d->nbins is the model's)
+inline int walk_launch(const qsc_obs_desc* d, const qsc_model* m, int R, WalkLaunch* wl) {
+  return walk_launch(d->K, d->Pp, m, R, 0, wl);
+}
+
+// the element-wise calls (qsc_entry_*): their argument check and their grid (grid-stride)
+inline bool entry_args_ok(const qsc_model* m, int64_t n, const void* Y, const void* T,
+                          const void* out) {
+  return info_model_ok(m) && n >= 0 && (n == 0 || (Y && T && out));
+}
+inline dim3 entry_grid(int64_t n) {
+  return dim3((unsigned)std::min<int64_t>(ceil_div(n, kBlock), 8192));
 }
 
 // QSC_CHOL_SOLVE's rules for a 2 x 2 system in fp64 (qsc_qfit.hip): Cholesky of the damped
@@ -173,12 +216,81 @@ __device__ __forceinline__ void chol2_solve_f64(const double (&a)[3], const bool
   }                                                                                       \
   for (int b_ = threadIdx.x; b_ < (lk).nbins; b_ += kBlock) El[b_] = (E_).e[b_];          \
   __syncthreads()
-// declares wave, lane, l, h (lane l + 32 h: half h of position l of the wave's slice), Ko, pad_value
-#define QSC_SLANE(E, SR, K)                                                               \
+// declares wave, lane, l, h (lane l + 32 h: half h of position l of the wave's slice)
+#define QSC_SLANE_GEOMETRY()                                                              \
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;                             \
-  const int l = lane & (QSC_SLICE - 1), h = lane >> 5;                                    \
+  const int l = lane & (QSC_SLICE - 1), h = lane >> 5
+// declares Ko and pad_value: what a clamped read of the lists returns
+#define QSC_SLANE_PAD(E, SR, K)                                                           \
   const int Ko = sr_off(K);                                                               \
   const uint32_t pad_value = SR ? 2u * (uint32_t)Ko : (Ent<E>::kPad << Ent<E>::kBits)
+// ... both
+#define QSC_SLANE(E, SR, K) \
+  QSC_SLANE_GEOMETRY();     \
+  QSC_SLANE_PAD(E, SR, K)
+
+// ---- the lists of slice s ----
+// declares nch (4-entry chunks of every list of the slice) and base (the lane's first pair);
+// reads width, off, l, h
+#define QSC_SLICE_LISTS(s)         \
+  const int nch = width[s] >> 2;   \
+  const int64_t base = off[s] + l * 4 + 2 * h
+
+// ---- the walk over the lane's entries of a slice, in list order ----
+// Between QSC_WALK_BEGIN and QSC_WALK_END stand the statements for one entry.  Declares for them
+// k, code, pad (decode's: clamped into range, a pad reads as k = code = 0), cv[RP] (the C^T row of
+// bin k: finite, so a pad's terms can be selected to exactly 0) and t = x . cv in fp32, r
+// ascending; reads ent, base, n_ent, nch, pad_value, K, Ko, lk, Cl.
+// The next chunk's pair is loaded while this one is worked.  Past the last list that read meets
+// the next slice's entries or the array's pad tail (QSC_ENTRY_TAIL) and is never used; load_pair
+// clamps it either way, so no read leaves the array.
+#define QSC_WALK_BEGIN(RP, CP, E, SR, x)                                                   \
+  {                                                                                        \
+    uint32_t n0_, n1_;                                                                     \
+    load_pair<E>(ent, base, n_ent, pad_value, n0_, n1_);                                   \
+    for (int ch_ = 0; ch_ < nch; ++ch_) {                                                  \
+      const uint32_t v_[2] = {n0_, n1_};                                                   \
+      load_pair<E>(ent, base + (int64_t)(ch_ + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0_, n1_); \
+      _Pragma("unroll") for (int e_ = 0; e_ < 2; ++e_) {                                   \
+        int k, code;                                                                       \
+        bool pad;                                                                          \
+        decode<E, SR>(v_[e_], K, Ko, lk.nbins, k, code, pad);                              \
+        float cv[RP];                                                                      \
+        QSC_ROW_LOAD(RP, cv, Cl + k * (CP))                                                \
+        float t = 0.0f;                                                                    \
+        _Pragma("unroll") for (int r_ = 0; r_ < (RP); ++r_) t = __builtin_fmaf((x)[r_], cv[r_], t);
+#define QSC_WALK_END \
+      }              \
+    }                \
+  }
+
+// ---- the block update J += hh y y^T on the packed upper triangle of the first N rows ----
+// J[tri(i, j)] += (hh y[i]) y[j] for i <= j < N: the product hh y[i] first, then the fma, rows
+// and columns ascending.  ROW: statements in i_ that a caller's own row sums run first in row i_
+// (may be empty).
+#define QSC_BLOCK_UPDATE(RP, N, J, hh, y, ROW)                                             \
+  _Pragma("unroll") for (int i_ = 0; i_ < (N); ++i_) {                                     \
+    ROW                                                                                    \
+    const float hi_ = (hh) * (y)[i_];                                                      \
+    _Pragma("unroll") for (int j_ = i_; j_ < (N); ++j_)                                    \
+        (J)[tri<RP>(i_, j_)] = __builtin_fmaf(hi_, (y)[j_], (J)[tri<RP>(i_, j_)]);         \
+  }
+
+// ---- the element-wise kernels (qsc_entry_*): a walk's device functions on n given (code, t) ----
+// declares se[], the edge table in LDS (EDGE: the edges of bin b_, an expression in b_); ends
+// with the workgroup barrier
+#define QSC_ENTRYWISE_STAGE(lk, EDGE)                                                      \
+  __shared__ float2 se[QSC_MAX_BOUNDS - 1];                                                \
+  for (int b_ = threadIdx.x; b_ < (lk).nbins; b_ += blockDim.x) se[b_] = (EDGE);           \
+  __syncthreads()
+// Between QSC_ENTRYWISE_BEGIN and QSC_ENTRYWISE_END stand the statements for element i of the
+// grid-stride loop.  Declares i and y (the code Y[i] clamped into [0, nbins)); reads Y, n.
+#define QSC_ENTRYWISE_BEGIN(lk)                                                            \
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;                  \
+       i += (int64_t)gridDim.x * blockDim.x) {                                             \
+    int64_t y = Y[i];                                                                      \
+    y = y < 0 ? 0 : (y >= (lk).nbins ? (lk).nbins - 1 : y);
+#define QSC_ENTRYWISE_END }
 
 // ---- one entry: its terms at t = x . y added to (ft, neg, gt, Jt) ----
 #define QSC_ENTRY_ACCUMULATE(RP, LOGIT, LOG, KIND, x, y, code, pad, El, lk, inv_a, ft, neg, gt, Jt) \
@@ -201,12 +313,7 @@ __device__ __forceinline__ void chol2_solve_f64(const double (&a)[3], const bool
     neg = neg || (eneg_ && !(pad));                                                        \
     ge_ = use_ ? ge_ : 0.0f;                                                               \
     hh_ = use_ ? hh_ : 0.0f;                                                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < (RP); ++i_) {                                  \
-      (gt)[i_] = __builtin_fmaf(ge_, (y)[i_], (gt)[i_]);                                   \
-      const float hi_ = hh_ * (y)[i_];                                                     \
-      _Pragma("unroll") for (int j_ = i_; j_ < (RP); ++j_)                                 \
-          (Jt)[tri<RP>(i_, j_)] = __builtin_fmaf(hi_, (y)[j_], (Jt)[tri<RP>(i_, j_)]);     \
-    }                                                                                      \
+    QSC_BLOCK_UPDATE(RP, RP, Jt, hh_, y, (gt)[i_] = __builtin_fmaf(ge_, (y)[i_], (gt)[i_]);) \
   }
 
 // ---- the walk of one slice at st: the halves summed, the ridge term added ----
@@ -219,22 +326,10 @@ __device__ __forceinline__ void chol2_solve_f64(const double (&a)[3], const bool
   bool neg = false;                                                                        \
   _Pragma("unroll") for (int r_ = 0; r_ < (RP); ++r_) gt[r_] = 0.0f;                       \
   _Pragma("unroll") for (int i_ = 0; i_ < (NT); ++i_) Jt[i_] = 0.0f;                       \
-  uint32_t n0_, n1_;                                                                       \
-  load_pair<E>(ent, base, n_ent, pad_value, n0_, n1_);                                     \
-  for (int ch_ = 0; ch_ < nch; ++ch_) {                                                    \
-    const uint32_t v_[2] = {n0_, n1_};                                                     \
-    /* the next chunk's entries while this one is worked (past the last list: the next */  \
-    /* slice's entries or the array's pad tail, QSC_ENTRY_TAIL; clamped in load_pair) */   \
-    load_pair<E>(ent, base + (int64_t)(ch_ + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0_, n1_); \
-    _Pragma("unroll") for (int e_ = 0; e_ < 2; ++e_) {                                     \
-      int k_, code_;                                                                       \
-      bool pad_;                                                                           \
-      decode<E, SR>(v_[e_], K, Ko, lk.nbins, k_, code_, pad_);                             \
-      float cv_[RP];                                                                       \
-      QSC_ROW_LOAD(RP, cv_, Cl + k_ * (CP))                                                \
-      QSC_ENTRY_ACCUMULATE(RP, LOGIT, LOG, KIND, st, cv_, code_, pad_, El, lk, inv_a, ft, neg, gt, Jt) \
-    }                                                                                      \
-  }                                                                                        \
+  QSC_WALK_BEGIN(RP, CP, E, SR, st)                                                        \
+  (void)t; /* (the entry's own t_ is the same sum) */                                      \
+  QSC_ENTRY_ACCUMULATE(RP, LOGIT, LOG, KIND, st, cv, code, pad, El, lk, inv_a, ft, neg, gt, Jt) \
+  QSC_WALK_END                                                                             \
   /* the two halves' partial sums: the same bits on both lanes from here on */             \
   ft += __shfl_xor(ft, 32, 64);                                                            \
   neg = neg || (__shfl_xor((int)neg, 32, 64) != 0);                                        \

@@ -384,8 +384,6 @@ bool n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API int qsc_obs_readings_count(const int32_t* k, const int32_t* p, const void* code,

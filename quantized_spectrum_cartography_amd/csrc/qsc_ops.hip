@@ -491,8 +491,6 @@ __global__ void __launch_bounds__(kBlock) perm_scatter_kernel(const float* __res
 // =======================================================================================
 // C ABI
 // =======================================================================================
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 #define DISPATCH_R(R, KERNEL, GRID, BLOCK, STREAMV, ...)                                 \
   do {                                                                                  \
     if ((R) <= 4) hipLaunchKernelGGL(KERNEL<4>, GRID, BLOCK, 0, STREAMV, __VA_ARGS__);   \

@@ -218,8 +218,6 @@ int dbg_line_fused(bool clear);
 }  // namespace qsc
 #endif
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 // launch KERNEL<RP> of the rank-templated update kernels for the padded rank RP
 #define QSC_LAUNCH_RP(KERNEL, RP, ...)                                  \
   do {                                                                  \

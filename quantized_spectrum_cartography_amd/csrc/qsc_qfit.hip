@@ -39,7 +39,6 @@
 //     finish:   accept / reject the last walked trial;  theta, F, covariance, steps, flags
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstddef>
 
 #include "qsc_common.cuh"
@@ -103,43 +102,25 @@ __global__ void __launch_bounds__(kBlock) qfit_walk_kernel(
 #pragma unroll
     for (int i = 0; i < kTerms; ++i) acc[i] = 0.0;
     bool neg = false;
-    const int nch = width[s] >> 2;  // 4-entry chunks of every list of the slice
-    const int64_t base = off[s] + l * 4 + 2 * h;
-    uint32_t n0, n1;
-    load_pair<E>(ent, base, n_ent, pad_value, n0, n1);
-    for (int ch = 0; ch < nch; ++ch) {
-      const uint32_t v[2] = {n0, n1};
-      // the next chunk's entries while this one is worked (past the last list: the next slice's
-      // entries or the array's pad tail, QSC_ENTRY_TAIL; clamped in load_pair either way)
-      load_pair<E>(ent, base + (int64_t)(ch + 1) * (QSC_SLICE * 4), n_ent, pad_value, n0, n1);
+    QSC_SLICE_LISTS(s);
+    QSC_WALK_BEGIN(RP, CP, E, SR, sv)
+      double td = 0.0;
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        int k, code;
-        bool pad;
-        decode<E, SR>(v[e], K, Ko, lk.nbins, k, code, pad);
-        float cv[RP];
-        QSC_ROW_LOAD(RP, cv, Cl + k * CP)
-        float t = 0.0f;
-#pragma unroll
-        for (int r = 0; r < RP; ++r) t = __builtin_fmaf(sv[r], cv[r], t);
-        double td = 0.0;
-#pragma unroll
-        for (int r = 0; r < RP; ++r) td = __builtin_fma((double)sv[r], (double)cv[r], td);
-        float fe, ge[2], he[3];
-        bool use, eneg;
-        entry_calib<LOGIT, LOG, KIND>(t, code, El, lk, fe, ge, he, use, eneg);
-        const double fd = entry_calib_nll<LOGIT, LOG>(fe, eneg, td, El[code], lk, inv_a);
-        // a pad adds exactly 0
-        use = use && !pad;
-        acc[0] += pad ? 0.0 : fd;
-        neg = neg || (eneg && !pad);
-        acc[1] += use ? (double)ge[0] : 0.0;
-        acc[2] += use ? (double)ge[1] : 0.0;
-        acc[3] += use ? (double)he[0] : 0.0;
-        acc[4] += use ? (double)he[1] : 0.0;
-        acc[5] += use ? (double)he[2] : 0.0;
-      }
-    }
+      for (int r = 0; r < RP; ++r) td = __builtin_fma((double)sv[r], (double)cv[r], td);
+      float fe, ge[2], he[3];
+      bool use, eneg;
+      entry_calib<LOGIT, LOG, KIND>(t, code, El, lk, fe, ge, he, use, eneg);
+      const double fd = entry_calib_nll<LOGIT, LOG>(fe, eneg, td, El[code], lk, inv_a);
+      // a pad adds exactly 0
+      use = use && !pad;
+      acc[0] += pad ? 0.0 : fd;
+      neg = neg || (eneg && !pad);
+      acc[1] += use ? (double)ge[0] : 0.0;
+      acc[2] += use ? (double)ge[1] : 0.0;
+      acc[3] += use ? (double)he[0] : 0.0;
+      acc[4] += use ? (double)he[1] : 0.0;
+      acc[5] += use ? (double)he[2] : 0.0;
+    QSC_WALK_END
     // the two halves of every position, then the 32 positions: the same bits on every lane
     int negi = neg ? 1 : 0;
 #pragma unroll
@@ -162,16 +143,10 @@ template <bool LOGIT, bool LOG, int KIND>
 __global__ void __launch_bounds__(kBlock) entry_calib_kernel(
     const int64_t* __restrict__ Y, const float* __restrict__ T, int64_t n, Link lk0, Edges E_,
     double a0, double tau, double beta, double* __restrict__ out) {
-  __shared__ float2 se[QSC_MAX_BOUNDS - 1];
   const Link lk = calib_link(lk0, LOGIT, a0, tau);
-  for (int b = threadIdx.x; b < lk.nbins; b += blockDim.x)
-    se[b] = calib_edges(E_.e[b], b, lk.nbins, LOG, beta);
-  __syncthreads();
+  QSC_ENTRYWISE_STAGE(lk, calib_edges(E_.e[b_], b_, lk.nbins, LOG, beta));
   const double inv_a = 1.0 / (double)lk.a;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t y = Y[i];
-    y = y < 0 ? 0 : (y >= lk.nbins ? lk.nbins - 1 : y);
+  QSC_ENTRYWISE_BEGIN(lk)
     const float t = T[i];
     float fe, ge[2], he[3];
     bool use, neg;
@@ -183,7 +158,7 @@ __global__ void __launch_bounds__(kBlock) entry_calib_kernel(
     out[3 * n + i] = use ? (double)he[0] : 0.0;
     out[4 * n + i] = use ? (double)he[1] : 0.0;
     out[5 * n + i] = use ? (double)he[2] : 0.0;
-  }
+  QSC_ENTRYWISE_END
 }
 
 // ---------------------------------------------------------------------------------------
@@ -330,25 +305,18 @@ __global__ void __launch_bounds__(kBlock) qfit_step_kernel(
   }
 }
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 int qfit_walk(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
               const int64_t* s_off, const qsc_model* m, int R, const float* S, const float* C,
-              int kind, void* ws, hipStream_t hs) {
-  const int RP = qsc_rank_pad(R);
-  const size_t shm = sinfo_lds(d->K, RP, d->nbins);
-  const Link lk = make_link(m);
-  Edges E;
-  make_edges(m, &E);
+              int kind, const WalkLaunch& wl, void* ws, hipStream_t hs) {
+  const int RP = wl.RP;
   const double a0 = qfit_a0(m);
-  const int nslices = d->Pp / QSC_SLICE;
-  const dim3 grid((unsigned)slice_grid(nslices, 8)), blk(kBlock);
+  const dim3 grid((unsigned)slice_grid(wl.nslices, 8)), blk(kBlock);
   const QfitState* st = static_cast<const QfitState*>(ws);
   double* part = qfit_partials(ws);
-#define QFIT_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                 \
-  hipLaunchKernelGGL((qfit_walk_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,        \
-                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
-                     a0, R, d->K, S, C, st, part)
+#define QFIT_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                              \
+  hipLaunchKernelGGL((qfit_walk_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, wl.shm, hs,  \
+                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, wl.nslices, \
+                     wl.lk, wl.E, a0, R, d->K, S, C, st, part)
   QSC_LAYOUT_DISPATCH(QFIT_LAUNCH);
 #undef QFIT_LAUNCH
   QSC_CHECK_LAUNCH();
@@ -364,12 +332,13 @@ int qfit_step(const qsc_obs_desc* d, void* ws, int final_, double* theta_out, do
   return QSC_OK;
 }
 
-// the argument checks the three calls share; QSC_OK, or the code to return
-int qfit_check(const qsc_obs_desc* d, const qsc_model* m, int R, const void* ws, size_t ws_bytes) {
+// the argument checks the three calls share, then the walk's launch record; QSC_OK, or the code
+// to return
+int qfit_check(const qsc_obs_desc* d, const qsc_model* m, int R, const void* ws, size_t ws_bytes,
+               WalkLaunch* wl) {
   if (!d || !info_model_ok(m) || !info_layout_ok(d, m, R)) return QSC_EINVAL;
   if (!ws || ws_bytes < qfit_ws_bytes(d)) return QSC_EINVAL;
-  if (sinfo_lds(d->K, qsc_rank_pad(R), d->nbins) > kInfoLdsMax) return QSC_EUNSUPPORTED;
-  return QSC_OK;
+  return walk_launch(d, m, R, wl);
 }
 
 }  // namespace
@@ -393,7 +362,8 @@ QSC_API int qsc_qfit_begin(const qsc_obs_desc* d, const void* s_entries, const i
   if (fit_mask < 1 || fit_mask > (FIT_SCALE | FIT_SHIFT)) return QSC_EINVAL;
   if (!(prior_scale >= 0.0) || !(prior_shift >= 0.0) || !(tau0 == tau0) || !(beta0 == beta0))
     return QSC_EINVAL;
-  const int rc = qfit_check(d, m, R, ws, ws_bytes);
+  WalkLaunch wl;
+  const int rc = qfit_check(d, m, R, ws, ws_bytes, &wl);
   if (rc != QSC_OK) return rc;
   if (d->s_entries > 0 && !s_entries) return QSC_EINVAL;
   QfitState init = {};
@@ -409,7 +379,7 @@ QSC_API int qsc_qfit_begin(const qsc_obs_desc* d, const void* s_entries, const i
   hipStream_t hs = STREAM(stream);
   hipLaunchKernelGGL(qfit_init_kernel, dim3(1), dim3(64), 0, hs, static_cast<QfitState*>(ws), init);
   QSC_CHECK_LAUNCH();
-  return qfit_walk(d, s_entries, s_width, s_off, m, R, S, C, kind, ws, hs);
+  return qfit_walk(d, s_entries, s_width, s_off, m, R, S, C, kind, wl, ws, hs);
 }
 
 QSC_API int qsc_qfit_iterate(const qsc_obs_desc* d, const void* s_entries, const int32_t* s_width,
@@ -418,13 +388,14 @@ QSC_API int qsc_qfit_iterate(const qsc_obs_desc* d, const void* s_entries, const
                              void* stream) {
   if (!s_width || !s_off || !S || !C) return QSC_EINVAL;
   if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
-  const int rc = qfit_check(d, m, R, ws, ws_bytes);
+  WalkLaunch wl;
+  const int rc = qfit_check(d, m, R, ws, ws_bytes, &wl);
   if (rc != QSC_OK) return rc;
   if (d->s_entries > 0 && !s_entries) return QSC_EINVAL;
   hipStream_t hs = STREAM(stream);
   const int rs = qfit_step(d, ws, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hs);
   if (rs != QSC_OK) return rs;
-  return qfit_walk(d, s_entries, s_width, s_off, m, R, S, C, kind, ws, hs);
+  return qfit_walk(d, s_entries, s_width, s_off, m, R, S, C, kind, wl, ws, hs);
 }
 
 QSC_API int qsc_qfit_finish(const qsc_obs_desc* d, const qsc_model* m, int32_t R,
@@ -432,14 +403,15 @@ QSC_API int qsc_qfit_finish(const qsc_obs_desc* d, const qsc_model* m, int32_t R
                             int32_t* steps, int32_t* flags, void* ws, size_t ws_bytes,
                             void* stream) {
   if (!theta_out || !f_out || !flags) return QSC_EINVAL;
-  const int rc = qfit_check(d, m, R, ws, ws_bytes);
+  WalkLaunch wl;
+  const int rc = qfit_check(d, m, R, ws, ws_bytes, &wl);
   if (rc != QSC_OK) return rc;
   return qfit_step(d, ws, 1, theta_out, f_out, cov_out, gh_out, steps, flags, STREAM(stream));
 }
 
 QSC_API int qsc_entry_calib(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
                             double tau, double beta, int32_t kind, double* out, void* stream) {
-  if (!info_model_ok(m) || n < 0 || (n > 0 && (!Y || !T || !out))) return QSC_EINVAL;
+  if (!entry_args_ok(m, n, Y, T, out)) return QSC_EINVAL;
   if (kind != INFO_EXPECTED && kind != INFO_OBSERVED) return QSC_EINVAL;
   if (!(tau == tau) || !(beta == beta)) return QSC_EINVAL;
   if (n == 0) return QSC_OK;
@@ -447,8 +419,7 @@ QSC_API int qsc_entry_calib(const int64_t* Y, const float* T, int64_t n, const q
   Edges E;
   make_edges(m, &E);
   const double a0 = qfit_a0(m);
-  const int64_t want = ceil_div(n, kBlock);
-  const dim3 grid((unsigned)std::min<int64_t>(want, 8192)), blk(kBlock);
+  const dim3 grid = entry_grid(n), blk(kBlock);
   hipStream_t hs = STREAM(stream);
 #define CALIB_LAUNCH(LGT, LOGV, KD)                                                            \
   hipLaunchKernelGGL((entry_calib_kernel<LGT, LOGV, KD>), grid, blk, 0, hs, Y, T, n, lk, E, a0, \

@@ -98,8 +98,7 @@ __global__ void __launch_bounds__(kBlock) sfit_smooth_kernel(
     float mu = pr.mu0;
     bool done = !own, ident = false, step_ok = true;
     int nwalk = 0;
-    const int nch = width[s] >> 2;  // 4-entry chunks of every list of the slice
-    const int64_t base = off[s] + l * 4 + 2 * h;
+    QSC_SLICE_LISTS(s);
     for (int it = 0;; ++it) {
       // ---- walk: (ft, gt, Jt) at st (sfit_kernel's) ----
       QSC_WALK_SLICE(RP, NT, CP, E, SR, LOGIT, LOG, KIND, st, pr.ridge);
@@ -258,8 +257,6 @@ __global__ void __launch_bounds__(kBlock) sfit_smooth_kernel(
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API size_t qsc_sfit_smooth_workspace_bytes(const qsc_obs_desc* d, int32_t R) {
@@ -287,24 +284,21 @@ QSC_API int qsc_sfit_smooth(const qsc_obs_desc* d, const void* s_entries, const 
   if ((int64_t)d->Pp > kSmoothMaxPp) return QSC_EUNSUPPORTED;
   const size_t need = newton_ws_bytes(d, R);
   if (need > 0 && (!ws || ws_bytes < need)) return QSC_EINVAL;
-  const int RP = qsc_rank_pad(R);
-  const size_t shm = sinfo_lds(d->K, RP, d->nbins);
-  if (shm > kInfoLdsMax) return QSC_EUNSUPPORTED;
-  const Link lk = make_link(m);
-  Edges E;
-  make_edges(m, &E);
-  const int nslices = d->Pp / QSC_SLICE;
+  WalkLaunch wl;
+  const int rc = walk_launch(d, m, R, &wl);
+  if (rc != QSC_OK) return rc;
+  const int RP = wl.RP;
   const bool huber = smooth_kind == SMOOTH_HUBER;
   const SfsParams pr = {ridge, mu0, tol, inner_steps, project != 0, color, J, d->Pp, huber ? 1 : 0,
                         weight, huber ? delta : 0.0f, huber ? 1.0f / delta : 1.0f};
-  const dim3 grid((unsigned)newton_grid(nslices, RP)), blk(kBlock);
+  const dim3 grid((unsigned)newton_grid(wl.nslices, RP)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   const int4* n4 = reinterpret_cast<const int4*>(nbr);
-#define SFS_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                   \
-  hipLaunchKernelGGL((sfit_smooth_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, shm, hs,       \
-                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, nslices, lk, E, \
-                     R, d->K, d->P, perm, n4, C, S, pr, f_out, nll_out, steps, n_moved,           \
-                     n_unconverged, n_unidentified, (float*)ws)
+#define SFS_LAUNCH(RPV, ET, SRV, LGT, LOGV, KD)                                                \
+  hipLaunchKernelGGL((sfit_smooth_kernel<RPV, ET, SRV, LGT, LOGV, KD>), grid, blk, wl.shm, hs, \
+                     (const ET*)s_entries, s_width, s_off, (int64_t)d->s_entries, wl.nslices,  \
+                     wl.lk, wl.E, R, d->K, d->P, perm, n4, C, S, pr, f_out, nll_out, steps,    \
+                     n_moved, n_unconverged, n_unidentified, (float*)ws)
   QSC_LAYOUT_DISPATCH(SFS_LAUNCH);
 #undef SFS_LAUNCH
   QSC_CHECK_LAUNCH();

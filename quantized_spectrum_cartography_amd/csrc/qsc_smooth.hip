@@ -181,8 +181,6 @@ inline size_t smooth_ws_bytes(int64_t Pp) {
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API size_t qsc_smooth_workspace_bytes(int32_t Pp) {

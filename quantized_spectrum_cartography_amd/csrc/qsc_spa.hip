@@ -570,8 +570,6 @@ size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" {
 
 QSC_API size_t qsc_syrk_workspace_bytes(int32_t K, int32_t P) {
