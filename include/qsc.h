@@ -427,6 +427,11 @@ QSC_API int qsc_cpass_nsq(const qsc_obs_desc* d, const void* c_entries, const in
  * of the C they read (the fixed order of qsc_sumsq_small): a K-slab solver all-reduces it in
  * place and hands it to qsc_cfinish as normsq_c_ext.  -1 on an invalid descriptor. */
 QSC_API int64_t qsc_pass_cnsq_offset(const qsc_obs_desc* d, int32_t R);
+/* byte offset, in the pass workspace, of the partials qsc_cfinish / qsc_state_flush sum (for
+ * tests that re-sum them).  which 0: the C-pass dC slab [ntiles][R][64 nks]; 1: the C-pass NLL
+ * partials [ntiles * nks]; 2, 3: the S-pass NLL and ||S||^2 partials [Pp / QSC_SLICE].  -1 on an
+ * invalid descriptor or `which`. */
+QSC_API int64_t qsc_pass_part_offset(const qsc_obs_desc* d, int32_t R, int32_t which);
 /* ||x||^2 into *out (fp32, fixed order), e.g. the local ||C_slab||^2 before an all-reduce */
 QSC_API int qsc_sumsq_small(const float* x, int32_t n, float* out, void* stream);
 /* Adam (torch.optim.Adam's update, bit for bit with torch 2.x's single-tensor CPU path) on a flat

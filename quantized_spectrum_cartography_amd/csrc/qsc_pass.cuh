@@ -65,7 +65,7 @@ constexpr int kCParts = kCBlock / 64;
 #ifndef QSC_CPART_MIN_CHUNKS
 #define QSC_CPART_MIN_CHUNKS 1.5
 #endif
-constexpr int kFBlock = 1024;  // C finish: 16 waves split the tile sum
+constexpr int kFBlock = 1024;  // qsc_cupdate's one workgroup (the C finish sizes its own)
 
 // occupancy targets (waves per SIMD) that bound the register allocation of the passes; the
 // rank-16 instances need twice the registers for the S/C row vectors

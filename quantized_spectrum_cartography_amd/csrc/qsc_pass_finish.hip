@@ -11,80 +11,111 @@ namespace {
 // The fixed order of the scalar partials -- the S-passes' per-slice NLL and ||S||^2
 // (part_nll_s, part_nsq_s) and the C-passes' per-(tile, k-slice) NLL (part_nll_c) -- which every
 // form settles (cfinish's book-keeping block, state_flush: both 1024-thread blocks), so that the
-// solver forms agree bit for bit: thread i sums items i, i + 1024, i + 2048, ... in order (every
-// load of a batch of 8 issued before the sums: one memory round trip at C3's 8192 slices instead
-// of a dependent chain per tile); then each wave's xor butterfly (wave_sum) and the 16 wave sums
-// in wave order; every sum from +0.
+// solver forms agree bit for bit: canonical thread i of kCanon = 1024 sums items i, i + 1024,
+// i + 2048, ... in order; then each canonical wave's xor butterfly (wave_sum) and the 16 wave sums
+// in wave order; every sum from +0.  A workgroup of 1024 / VF threads stands for the canonical one:
+// its thread t is the canonical threads t + f blockDim (f < VF), lane for lane.
+//
+// The totals are summed whether or not the state says they are pending, and so are never behind
+// a load of the state: the loads of a batch (8 items per canonical thread of each array) are all
+// issued before the first sum, beside the caller's read of the state words (state_in) -- one
+// memory round trip at C3's 8192 slices.  Thread 0 then keeps the totals that were pending
+// (settle_store); the workspace arrays always exist (carve), so the loads are in bounds.
 // ---------------------------------------------------------------------------------------
+constexpr int kCanon = 1024;
 struct Canon {
   float nll_s, nsq_s, nll_c;
 };
 
-__device__ __forceinline__ float canon_part(const float* __restrict__ x, int n, int tid, int nb) {
-  float a = 0.0f;
-  if (!x) return a;
-  for (int i0 = tid; i0 < n; i0 += 8 * nb) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = x[min(i0 + j * nb, n - 1)];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (i0 + j * nb < n) a += v[j];
-  }
-  return a;
-}
-
-// The three totals over nslices S-pass items and nc C-pass items; sh: LDS [3][nb / 64] floats.
+// The totals over nslices S-pass items and (WITH_C) nc C-pass items; sh: LDS [3][16] floats.
 // Result valid in thread 0.
-__device__ Canon canon_totals(const float* __restrict__ nll_s, const float* __restrict__ nsq_s,
-                              const float* __restrict__ nll_c, int nslices, int nc, float* sh) {
-  const int nb = blockDim.x, tid = threadIdx.x, nw = nb >> 6;
-  float a = canon_part(nll_s, nslices, tid, nb);
-  float b = canon_part(nsq_s, nslices, tid, nb);
-  float c = canon_part(nll_c, nc, tid, nb);
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  if ((tid & 63) == 0) {
-    sh[tid >> 6] = a;
-    sh[nw + (tid >> 6)] = b;
-    sh[2 * nw + (tid >> 6)] = c;
+template <int VF, bool WITH_C>
+__device__ __forceinline__ Canon canon_totals(const float* __restrict__ nll_s,
+                                              const float* __restrict__ nsq_s,
+                                              const float* __restrict__ nll_c, int nslices, int nc,
+                                              float* sh) {
+  constexpr int NB = kCanon / VF, NW = kCanon / 64;
+  const int tid = threadIdx.x;
+  float a[VF], b[VF], c[VF];
+#pragma unroll
+  for (int f = 0; f < VF; ++f) a[f] = b[f] = c[f] = 0.0f;
+  const int n = WITH_C ? max(nslices, nc) : nslices;
+  for (int i0 = 0; i0 < n; i0 += 8 * kCanon) {
+    float va[VF][8], vb[VF][8], vc[VF][8];
+#pragma unroll
+    for (int f = 0; f < VF; ++f)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = i0 + tid + f * NB + j * kCanon;
+        va[f][j] = nll_s[min(i, nslices - 1)];
+        vb[f][j] = nsq_s[min(i, nslices - 1)];
+        vc[f][j] = WITH_C ? nll_c[min(i, nc - 1)] : 0.0f;
+      }
+#pragma unroll
+    for (int f = 0; f < VF; ++f)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = i0 + tid + f * NB + j * kCanon;
+        if (i < nslices) {
+          a[f] += va[f][j];
+          b[f] += vb[f][j];
+        }
+        if (WITH_C && i < nc) c[f] += vc[f][j];
+      }
+  }
+#pragma unroll
+  for (int f = 0; f < VF; ++f) {
+    const float wa = wave_sum(a[f]), wb = wave_sum(b[f]), wc = wave_sum(c[f]);
+    const int w = (tid >> 6) + f * (NB / 64);  // the canonical wave
+    if ((tid & 63) == 0) {
+      sh[w] = wa;
+      sh[NW + w] = wb;
+      sh[2 * NW + w] = wc;
+    }
   }
   __syncthreads();
   Canon r{0.0f, 0.0f, 0.0f};
   if (tid == 0)
-    for (int w = 0; w < nw; ++w) {
+    for (int w = 0; w < NW; ++w) {
       r.nll_s += sh[w];
-      r.nsq_s += sh[nw + w];
-      r.nll_c += sh[2 * nw + w];
+      r.nsq_s += sh[NW + w];
+      r.nll_c += sh[2 * NW + w];
     }
   return r;
 }
 
-// book-keeping shared by cfinish (block 0) and state_flush: settle a pending S-pass
-__device__ void settle_s(qsc_state* __restrict__ st, const float* __restrict__ part_nll_s,
-                         const float* __restrict__ part_nsq_s, int nslices, float* hist,
-                         int hist_cap, float* sh) {
-  const int pend = st->pending;  // uniform read (all threads)
-  if (!(pend & (QSC_PEND_SNLL | QSC_PEND_SUPD))) return;
-  const Canon c = canon_totals(part_nll_s, (pend & QSC_PEND_SUPD) ? part_nsq_s : nullptr, nullptr,
-                               nslices, 0, sh);
-  if (threadIdx.x == 0) {
-    const int it = st->iter - 1;
-    st->nll_s = c.nll_s;
-    if (hist && it >= 0 && it < hist_cap) {
-      hist[4 * it + 0] = st->nll_c;
-      hist[4 * it + 1] = c.nll_s;
-      hist[4 * it + 2] = st->normsq_c;
-      hist[4 * it + 3] = st->normsq_s_prev;
-    }
-    if (pend & QSC_PEND_SUPD) {
-      st->normsq_s = c.nsq_s;
-      st->step_s += 1;
-    }
-    st->pending = pend & ~(QSC_PEND_SNLL | QSC_PEND_SUPD);
+// the state words the book-keeping needs, read together ahead of the totals (no load waits for
+// another's value)
+struct StateIn {
+  int step_c, step_s, iter, pending;
+  float normsq_s, normsq_c, nll_c, normsq_s_prev;
+};
+__device__ __forceinline__ StateIn state_in(const qsc_state* __restrict__ st) {
+  return StateIn{st->step_c,   st->step_s,   st->iter,  st->pending,
+                 st->normsq_s, st->normsq_c, st->nll_c, st->normsq_s_prev};
+}
+
+// book-keeping shared by cfinish and state_flush (thread 0): settle a pending S-pass from the
+// totals -- totals that are not pending are dropped -- and return the flags left pending (the
+// caller stores them); s.normsq_s follows the state
+__device__ __forceinline__ int settle_store(qsc_state* __restrict__ st, StateIn& s, const Canon& c,
+                                            float* __restrict__ hist, int hist_cap) {
+  const int pend = s.pending;
+  if (!(pend & (QSC_PEND_SNLL | QSC_PEND_SUPD))) return pend;
+  const int it = s.iter - 1;
+  st->nll_s = c.nll_s;
+  if (hist && it >= 0 && it < hist_cap) {
+    hist[4 * it + 0] = s.nll_c;
+    hist[4 * it + 1] = c.nll_s;
+    hist[4 * it + 2] = s.normsq_c;
+    hist[4 * it + 3] = s.normsq_s_prev;
   }
-  __syncthreads();
+  if (pend & QSC_PEND_SUPD) {
+    s.normsq_s = c.nsq_s;
+    st->normsq_s = c.nsq_s;
+    st->step_s = s.step_s + 1;
+  }
+  return pend & ~(QSC_PEND_SNLL | QSC_PEND_SUPD);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -100,136 +131,98 @@ __device__ void settle_s(qsc_state* __restrict__ st, const float* __restrict__ p
 #define QSC_CF_ARGS                                                                           \
   slab, ntiles, nks, R, K, C, mode, dC, mC, vC, ad, lambda_c, normsq_ext, cnsq, st, part_nll_c,  \
       npart_c, part_nll_s, part_nsq_s, nslices, hist, hist_cap, acache
-constexpr int kFWaves = kFBlock / 64;
+// Bins per column block.  A column's gradient is the sum of kFParts = 16 partials in partial
+// order, partial w the sum of tiles w, w + 16, ... in order (the canonical tile groups), every sum
+// from +0.  A block of 16 * kFGroup threads takes kFGroup bins of one r: thread t holds bin
+// t % kFGroup of partial t / kFGroup with sixteen independent loads in flight.  64: one wave per
+// partial, 256-byte rows, C3's 2 MB slab pulled by 32 workgroups of 1024 threads.  Spreading it
+// over more CUs lost at C3 -- 32-bin groups (64 workgroups of 512) +1.0 %, 16-bin groups (128 of
+// 256, 64-byte rows) -1.1 % against 64's +2.3 % over the parent's headline
+// (profiles/cfinish/bench_headline_parent_vs_this.txt); the orders are the same at every size
+// (tests/test_gpu_cfinish_order.py passes at 16, 32 and 64).
+#ifndef QSC_CFIN_GROUP
+#define QSC_CFIN_GROUP 64
+#endif
+constexpr int kFGroup = QSC_CFIN_GROUP, kFParts = 16;
+constexpr int kFinBlock = kFParts * kFGroup;
+static_assert(kFGroup == 16 || kFGroup == 32 || kFGroup == 64, "a 64-bin slice in whole groups");
 
-// the C-finish tile sum of the VF virtual waves vw = wave + f NWp (f < VF) of this wave: each
-// virtual wave's column partial sums its tiles vw, vw + 16, ... in order; sixteen loads in
-// flight per lane (16 / VF tiles of each virtual wave per batch), so a 4..15-wave workgroup
-// holds no more registers for it than the 16-wave one
-template <int VF>
-__device__ __forceinline__ void cfin_tile_sum(float (*red)[64], const float* col,
-                                              const int64_t tstride, const int ntiles,
-                                              const int wave, const int NWp, const int lane) {
-  // NGB: groups of 16 NW tiles per batch.  Two in the standalone C-finish (32 loads in flight)
-  // made it slower, 3.26 -> 4.6 us at C3 (profiles/r04/fin_small_wg/ab_c3_grouped_tickets.log)
-  constexpr int NW = kFWaves, JB = 16 / VF, NGB = 1;
-  float a[VF];
-#pragma unroll
-  for (int f = 0; f < VF; ++f) a[f] = 0.0f;
-  for (int tg = 0; tg < ntiles; tg += NGB * 16 * NW) {
-    for (int jb = 0; jb < 16; jb += JB) {
-      float v[NGB][VF][JB];
-#pragma unroll
-      for (int gb = 0; gb < NGB; ++gb)
-#pragma unroll
-        for (int f = 0; f < VF; ++f) {
-          const int vw = wave + f * NWp;
-#pragma unroll
-          for (int j = 0; j < JB; ++j) {
-            const int tt = tg + gb * 16 * NW + vw + (jb + j) * NW;
-            v[gb][f][j] =
-                vw < NW ? col[(int64_t)min(tt, ntiles - 1) * tstride] : 0.0f;
-          }
-        }
-#pragma unroll
-      for (int gb = 0; gb < NGB; ++gb)
-#pragma unroll
-        for (int f = 0; f < VF; ++f) {
-          const int vw = wave + f * NWp;
-#pragma unroll
-          for (int j = 0; j < JB; ++j)
-            if (vw < NW && tg + gb * 16 * NW + vw + (jb + j) * NW < ntiles) a[f] += v[gb][f][j];
-        }
-    }
-  }
-#pragma unroll
-  for (int f = 0; f < VF; ++f)
-    if (wave + f * NWp < NW) red[wave + f * NWp][lane] = a[f];
-}
-
-// C-finish work item vb of R*nks + 2 (cfinish_kernel: vb = the workgroup), with its LDS scratch
-// passed in: per (r, 64-bin slice) column block the 16 waves' partials (wave w: tiles w, w + 16,
-// ... in order -- the canonical tile groups, canon_totals) summed in wave order; item R*nks the
-// book-keeping (canon_totals), item R*nks + 1 the next C-step's Adam scalars.
-__device__ __forceinline__ void cfinish_vb(const int vb, float (*red)[64], Scalars& sc, float* sh,
-                                           QSC_CF_PARAMS) {
-  constexpr int NW = kFWaves;
-  const int NWp = NW;
-  const int Kp = nks * 64;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+// Workgroup vb of R * Kp / kFGroup + 2: a column block per (r, kFGroup bins); then the
+// book-keeping block (canon_totals, settle_store) and the block of the next C-step's Adam
+// scalars.  Every block makes one round of loads: none waits for another load's value.
+__global__ void __launch_bounds__(kFinBlock) cfinish_kernel(QSC_CF_PARAMS) {
+  __shared__ float red[kFParts][kFGroup];
+  __shared__ Scalars sc;
+  __shared__ float sh[3 * (kCanon / 64)];
+  const int Kp = nks * 64, ngk = Kp / kFGroup, ncol = R * ngk;
+  const int vb = (int)blockIdx.x, tid = (int)threadIdx.x;
 
   // ||C||^2 of the C this step differentiates: written by the C-pass (C is read-only there),
   // or the caller's global value (K-slab); never re-read here, where blocks overwrite C
   const float nsq = normsq_ext ? *normsq_ext : *cnsq;
 
-  if (vb == R * nks + 1) {
+  if (vb == ncol + 1) {
     // the next C-step's Adam scalars (the next S-pass settles step_c + 1 in between)
-    if (mode == 1 && threadIdx.x == 0) adam_cache_store(acache, ad, st->step_c + 2);
+    if (mode == 1 && tid == 0) adam_cache_store(acache, ad, st->step_c + 2);
     return;
   }
-  if (vb == R * nks) {
-    // book-keeping block: settle the S-pass partials (settle_s) and total the C-pass NLL, in
-    // the canonical order (canon_totals)
-    const int pend = st->pending;
-    const bool settle = (pend & (QSC_PEND_SNLL | QSC_PEND_SUPD)) != 0;
-    const bool supd = (pend & QSC_PEND_SUPD) != 0;
-    const Canon cs = canon_totals(settle ? part_nll_s : nullptr, supd ? part_nsq_s : nullptr,
-                                  part_nll_c, nslices, npart_c, sh);
-    if (threadIdx.x == 0) {
-      int pnd = pend;
-      if (settle) {  // settle_s, thread-0 part
-        const int it = st->iter - 1;
-        st->nll_s = cs.nll_s;
-        if (hist && it >= 0 && it < hist_cap) {
-          hist[4 * it + 0] = st->nll_c;
-          hist[4 * it + 1] = cs.nll_s;
-          hist[4 * it + 2] = st->normsq_c;
-          hist[4 * it + 3] = st->normsq_s_prev;
-        }
-        if (supd) {
-          st->normsq_s = cs.nsq_s;
-          st->step_s += 1;
-        }
-        pnd = pend & ~(QSC_PEND_SNLL | QSC_PEND_SUPD);
-        st->pending = pnd;
-      }
+  if (vb == ncol) {
+    // book-keeping block: settle the S-pass partials and total the C-pass NLL, in the canonical
+    // order
+    StateIn s = state_in(st);
+    const Canon cs = canon_totals<kCanon / kFinBlock, true>(part_nll_s, part_nsq_s, part_nll_c,
+                                                            nslices, npart_c, sh);
+    if (tid == 0) {
+      int pnd = settle_store(st, s, cs, hist, hist_cap);
       st->nll_c = cs.nll_c;
       if (mode == 1) {
         st->normsq_c = nsq;
-        st->pending = pnd | QSC_PEND_C;
+        pnd |= QSC_PEND_C;
       }
-      if (mode == 2) dC[(int64_t)R * K] = st->normsq_s;  // this shard's ||S||^2 (IJ-slab)
+      if (pnd != s.pending) st->pending = pnd;
+      if (mode == 2) dC[(int64_t)R * K] = s.normsq_s;  // this shard's ||S||^2 (IJ-slab)
     }
     return;
   }
 
-  const int r = vb / nks, ks = vb - r * nks;
-  const int k = ks * 64 + lane;
-  // wave 0 reads its C / moments ahead of the tile sum (one HBM round trip instead of two)
+  const int r = vb / ngk, k0 = (vb - r * ngk) * kFGroup;
+  if (k0 >= K) return;  // padding bins only
+  const int w = tid / kFGroup, b = tid % kFGroup, k = k0 + b;
+  const int64_t i = (int64_t)r * K + k;
+  // the update's inputs ride in the round of the tile loads
   float p0 = 0.0f, m0 = 0.0f, v0 = 0.0f;
-  if (mode == 1 && wave == 0 && k < K) {
-    const int64_t i = (int64_t)r * K + k;
+  if (mode == 1 && w == 0 && k < K) {
     p0 = C[i];
     m0 = mC[i];
     v0 = vC[i];
   }
-  if (threadIdx.x == 0 && mode == 1) {
+  if (tid == 0 && mode == 1) {
     const AdamCache a0 = acache[0], a1 = acache[1];  // both slots: no dependent read on step_c
     const int step = st->step_c + 1;
     const float nrm = sqrtf(nsq);
     sc.coef = nrm > 0.0f ? lambda_c / nrm : 0.0f;
     sc.as = adam_scalars_cached((step & 1) ? a1 : a0, ad, step);
   }
-  // tile sum: (virtual) wave w takes tiles w, w+16, ...; sixteen independent loads in flight
+  // tile sum of partial w.  Thirty-two loads in flight per lane made the 1024-thread form slower,
+  // 3.26 -> 4.6 us at C3 (profiles/r04/fin_small_wg/ab_c3_grouped_tickets.log)
   const float* col = slab + (int64_t)r * Kp + k;
   const int64_t tstride = (int64_t)R * Kp;
-  cfin_tile_sum<1>(red, col, tstride, ntiles, wave, NWp, lane);
-  __syncthreads();
-  if (wave == 0 && k < K) {
-    float g = red[0][lane];
+  float a = 0.0f;
+  for (int tg = 0; tg < ntiles; tg += 16 * kFParts) {
+    float v[16];
 #pragma unroll
-    for (int w = 1; w < NW; ++w) g += red[w][lane];
-    const int64_t i = (int64_t)r * K + k;
+    for (int j = 0; j < 16; ++j)
+      v[j] = col[(int64_t)min(tg + w + j * kFParts, ntiles - 1) * tstride];
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (tg + w + j * kFParts < ntiles) a += v[j];
+  }
+  red[w][b] = a;
+  __syncthreads();
+  if (w == 0 && k < K) {
+    float g = red[0][b];
+#pragma unroll
+    for (int q = 1; q < kFParts; ++q) g += red[q][b];
     if (mode == 1) {
       float p = p0, m = m0, v = v0;
       g = __fadd_rn(g, __fmul_rn(p, sc.coef));
@@ -242,14 +235,6 @@ __device__ __forceinline__ void cfinish_vb(const int vb, float (*red)[64], Scala
     }
   }
 }
-
-__global__ void __launch_bounds__(kFBlock) cfinish_kernel(QSC_CF_PARAMS) {
-  __shared__ float red[kFWaves][64];
-  __shared__ Scalars sc;
-  __shared__ float sh[3 * kFWaves];
-  cfinish_vb((int)blockIdx.x, red, sc, sh, QSC_CF_ARGS);
-}
-
 
 // ---------------------------------------------------------------------------------------
 // C update from an externally reduced gradient g [R][K] (IJ-slab sharding, after the RCCL
@@ -291,11 +276,17 @@ __global__ void __launch_bounds__(1024) flush_kernel(qsc_state* __restrict__ st,
                                                      const float* __restrict__ part_nsq_s,
                                                      int ntiles, int nslices,
                                                      float* __restrict__ hist, int hist_cap) {
-  __shared__ float sh[3 * 16];
-  settle_s(st, part_nll_s, part_nsq_s, nslices, hist, hist_cap, sh);
-  if (threadIdx.x == 0 && (st->pending & QSC_PEND_C)) {
-    st->step_c += 1;
-    st->pending &= ~QSC_PEND_C;
+  __shared__ float sh[3 * (kCanon / 64)];
+  StateIn s = state_in(st);
+  const Canon cs =
+      canon_totals<1, false>(part_nll_s, part_nsq_s, nullptr, nslices, 0, sh);
+  if (threadIdx.x == 0) {
+    int pnd = settle_store(st, s, cs, hist, hist_cap);
+    if (pnd & QSC_PEND_C) {
+      st->step_c = s.step_c + 1;
+      pnd &= ~QSC_PEND_C;
+    }
+    if (pnd != s.pending) st->pending = pnd;
   }
 }
 
@@ -486,6 +477,14 @@ QSC_API int64_t qsc_pass_cnsq_offset(const qsc_obs_desc* d, int32_t R) {
                    base);
 }
 
+QSC_API int64_t qsc_pass_part_offset(const qsc_obs_desc* d, int32_t R, int32_t which) {
+  if (!desc_ok(d) || R < 1 || R > QSC_MAX_R || which < 0 || which > 3) return -1;
+  const uintptr_t base = 4096;
+  const PassWs w = carve(d, R, reinterpret_cast<void*>(base));
+  const float* part[4] = {w.slab, w.cnll, w.snll, w.snsq};
+  return (int64_t)(reinterpret_cast<uintptr_t>(part[which]) - base);
+}
+
 QSC_API int qsc_obs_signed_rows_ok(const qsc_obs_desc* d, int32_t R, const qsc_model* m) {
   if (!desc_ok(d) || !m || R < 1 || R > QSC_MAX_R || m->nbounds - 1 != d->nbins) return 0;
   return (is_onebit_cf(lik_kind(m)) && sr_layout_ok(d, R)) ? 1 : 0;
@@ -508,8 +507,8 @@ QSC_API int qsc_cfinish(const qsc_obs_desc* d, int32_t R, float* C, int32_t mode
   PassWs w = carve(d, R, ws);
   qsc_adam ad{};
   if (adam) ad = *adam;
-  hipLaunchKernelGGL(cfinish_kernel, dim3((unsigned)(R * d->nks + 2)), dim3(kFBlock), 0,
-                     STREAM(stream), w.slab, d->ntiles, d->nks, R, d->K, C, mode, dC, mC, vC, ad,
+  hipLaunchKernelGGL(cfinish_kernel, dim3((unsigned)(R * d->nks * (64 / kFGroup) + 2)),
+                     dim3(kFinBlock), 0, STREAM(stream), w.slab, d->ntiles, d->nks, R, d->K, C, mode, dC, mC, vC, ad,
                      lambda_c, normsq_c_ext, w.cnsq, st, w.cnll, d->ntiles * d->nks, w.snll,
                      w.snsq, d->Pp / QSC_SLICE, hist, hist_cap, w.acache + 2);
   QSC_CHECK_LAUNCH();
