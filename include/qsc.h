@@ -1067,6 +1067,70 @@ QSC_API int qsc_qfit_finish(const qsc_obs_desc* d, const qsc_model* m, int32_t R
 QSC_API int qsc_entry_calib(const int64_t* Y, const float* T, int64_t n, const qsc_model* m,
                             double tau, double beta, int32_t kind, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Draw readings from the model at (S, C), at the observed cells only, into the packed layout
+ * that already exists (qsc_draw.hip): the primitive of the parametric bootstrap and of
+ * simulation from a truth.  Not in the reference.  qsc_quantize adds noise to a dense map and
+ * bins it; a draw here uses the very P_b the likelihood evaluates.
+ *   One reading at bin k, pixel p (natural index i J + j), occurrence j_occ (0 for the first
+ *   reading of the cell (k, p), 1 for the second, ...; always 0 for dense codes), replicate rep:
+ *     t    = s_p . c_k                fp32, r ascending, by fma
+ *     x    = t  (linear model)  or  log(t + offset)
+ *     P_b  = qsc_sinfo's P of bin b = 0 .. nbins - 1 at x (the same device function: the edges as
+ *            the likelihood forms them, the truncated 1.414213, the mirroring and saturation rules)
+ *     Z    = sum_b P_b                fp32, b ascending
+ *     n    = x0 >> 8,  (x0, x1, x2, x3) = Philox4x32-10(counter, key)      24 bits
+ *     u    = (n + 1/2) 2^-24          0 < u < 1; as an fp32 NUMBER u would round to 1 for
+ *                                     n = 2^24 - 1 (n + 1/2 has 25 bits), so u itself is never
+ *                                     formed in fp32:
+ *     thr  = RN_fp32((n + 1/2) 2^-24 Z)        = fma(n, Zs, Zs / 2), Zs = Z 2^-24: one rounding
+ *     code = the smallest b with thr < sum_{b' <= b} P_b' (running fp32 sum, b ascending);
+ *            if no bin passes (thr rounded up to the last sum), the last b with P_b > 0
+ *   A bin whose fp32 P_b is 0 is never drawn (thr < cum_b and thr >= cum_{b-1} need P_b > 0), so
+ *   the NLL of drawn data never meets -log FLT_MIN.  Two bins: the same rule, one comparison.
+ *   Log model with t + offset <= 0: the reading keeps the code it has and *invalid (device
+ *   int32; the caller zeroes it; an integer atomic) is incremented, once per reading.  A reading
+ *   whose every P_b is 0 or NaN (a NaN t) keeps its code as well.  Nothing is NaN.
+ *   Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
+ *   SC'11), all arithmetic on uint32:
+ *     counter (c0, c1, c2, c3) = (k, p, j_occ, rep);  key (k0, k1) = (seed & 0xFFFFFFFF, seed >> 32)
+ *     ten times:  (hi0, lo0) = 0xD2511F53 * c0   (the 64-bit product's halves)
+ *                 (hi1, lo1) = 0xCD9E8D57 * c2
+ *                 (c0, c1, c2, c3) = (hi1 ^ c1 ^ k0,  lo1,  hi0 ^ c3 ^ k1,  lo0)
+ *                 (k0, k1) = (k0 + 0x9E3779B9, k1 + 0xBB67AE85)      (unused after the tenth)
+ *     x0 = c0.  Known answer: the all-zero counter and key give 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ *   A reading's draw is a function of (seed, rep, k, p, j_occ) and the model at its cell alone:
+ *   not of the tile, pixel order, list schedule, entry format, grid, or dense / readings input.
+ * Both calls: asynchronous on `stream`, no allocation, no workspace, no floating-point atomics,
+ * capturable.  QSC_EINVAL for m->loss == QSC_LOSS_SQUARED (not a likelihood) or a bad model, a
+ * null pointer, R outside [1, QSC_MAX_R], replicate < 0, shapes out of range or a model / layout
+ * mismatch; QSC_EUNSUPPORTED, before any launch, where a kernel's tables do not fit the LDS.
+ * ------------------------------------------------------------------------------------- */
+/* Dense: codes[K][P] (0xFF = unobserved) -> codes_out[K][P] (another array).  Unobserved cells
+ * stay 0xFF; an observed cell gets its draw with j_occ = 0 (a code outside [0, nbins) is copied).
+ * S is read as natural planes [R][P], C as [R][K]: a workgroup works on consecutive pixels of one
+ * bin, so that plane reads are coalesced and c_k is uniform; position rows would need the inverse
+ * pixel order and scatter.  The observed cells of a tile are compacted in LDS before the bin loop
+ * (about one cell in ten is observed: a thread per cell would idle nine lanes in ten there). */
+QSC_API int qsc_draw_codes(const uint8_t* codes, int32_t K, int32_t P, const qsc_model* m,
+                           int32_t R, const float* S, const float* C, int64_t seed,
+                           int32_t replicate, uint8_t* codes_out, int32_t* invalid, void* stream);
+/* Readings: `packed` (qsc_obs_readings_layout's sorted readings, packed_bytes of them, n = d->nnz
+ * readings) -> packed_out (another array of packed_bytes): the segment tables are copied, and the
+ * code of every sorted reading is replaced in BOTH sorted arrays.  j_occ is a reading's place in
+ * its run of equal keys (found by looking back along the run, at most max_repeat long); both
+ * arrays are stable sorts of one list, so reading j_occ of a cell is the same reading in both and
+ * receives the same code.  (k, p) of an S-format reading: k from the reading, the position from
+ * the segment table, p = perm[position]; of a C-format reading: the bin from the tile's segment
+ * table, the position from qlocal by the tile rule, p = perm[position].  S in position order
+ * [Pp][RP] (the order of both arrays' keys), C [R][K], perm[Pp] as qsc_obs_readings_layout took it.
+ * Follow with qsc_obs_readings_fill (and qsc_obs_schedule) on packed_out for the entry arrays. */
+QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n,
+                              const qsc_obs_desc* d, const int32_t* perm, const qsc_model* m,
+                              int32_t R, const float* S, const float* C, int64_t seed,
+                              int32_t replicate, void* packed_out, int32_t* invalid,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

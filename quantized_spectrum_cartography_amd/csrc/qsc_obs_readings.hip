@@ -10,24 +10,21 @@
 // layout.  Integer atomics are used for counts only; the packed bytes depend on the input order
 // alone (equal keys keep it: the sort is stable), never on grid or wave order.
 //
-// The sorted readings are kept by the caller (`packed`, qsc_obs_readings_packed_bytes): a sorted
-// reading is  idx | code << 24  (idx = k or qlocal < 2^24, the wide format's own bound), from
-// which qsc_obs_readings_fill writes either entry format again without a dense codes array.
+// The sorted readings are kept by the caller (`packed`, qsc_obs_readings_packed_bytes; their layout
+// is qsc_obs_readings.cuh's): a sorted reading is  idx | code << 24  (idx = k or qlocal < 2^24, the
+// wide format's own bound), from which qsc_obs_readings_fill writes either entry format again
+// without a dense codes array.
 #include <hipcub/hipcub.hpp>
 
 #include "qsc_common.cuh"
 #include "qsc_obs_fmt.cuh"
+#include "qsc_obs_readings.cuh"
 
 using namespace qsc;
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kIdxBits = 24;
-constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1;
-
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ int code_at(const void* code, int code_bytes, int64_t i) {
   return code_bytes == 1 ? (int)((const uint8_t*)code)[i] : ((const int32_t*)code)[i];
 }
@@ -182,17 +179,6 @@ __global__ void __launch_bounds__(kBlock) rd_c_order_kernel(const int* __restric
   if (t == 0 && threadIdx.x == 0) sizes[(int64_t)gridDim.x * nks] = 0;  // the scan's total slot
 }
 
-// the list l of `nl` contiguous segments that holds sorted reading e: seg[l] <= e < seg[l + 1]
-// (seg[0] <= e < seg[nl] on entry; empty segments are stepped over)
-__device__ __forceinline__ int seg_find(const int* seg, int nl, int e) {
-  int lo = 0, hi = nl;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // S-format fill, one wave per slice: the slice's 32 lists are one contiguous run of the sorted
 // readings, read coalesced; each reading finds its list in the 33 segment bounds (LDS) and is
 // stored at its chunked slot.  Then the slice's slots are swept in address order for the pads.
@@ -290,46 +276,6 @@ size_t cub_scan64_bytes(int64_t n) {
   return b;
 }
 
-// shapes both calls derive from (K, P, PT)
-struct Dims {
-  int64_t Pp, ns, nt, nks, Kp, nc, nb;  // nb = nt * Kp bins, nc = nt * nks blocks
-};
-bool dims_of(int32_t K, int32_t P, int32_t PT, Dims* d) {
-  if (K < 1 || P < 1 || PT < 64 || (PT & 63)) return false;
-  d->Pp = round_up(P, PT);
-  d->ns = d->Pp / QSC_SLICE;
-  d->nt = d->Pp / PT;
-  d->nks = ceil_div(K, 64);
-  d->Kp = d->nks * 64;
-  d->nc = d->nt * d->nks;
-  d->nb = d->nt * d->Kp;
-  // every table is indexed and scanned with int
-  return d->Pp < (int64_t)1 << 31 && d->nb < ((int64_t)1 << 31) - 1;
-}
-
-// the caller-kept sorted readings
-struct Packed {
-  uint32_t* s_rd;  // [n]  k | code << 24, by (position, k)
-  uint32_t* c_rd;  // [n]  qlocal | code << 24, by (tile, bin, qlocal)
-  int* s_seg;      // [Pp + 1]  first sorted reading of every position's list
-  int* c_seg;      // [nt * Kp + 1]  ... of every (tile, bin) list, bins in k order
-  int* c_kinv;     // [nt * Kp]  place of bin k in the tile's c_kmap
-};
-size_t packed_carve(char* b, int64_t n, const Dims& d, Packed* pk) {
-  char* w = b;
-  pk->s_rd = (uint32_t*)w;
-  w += align_up((size_t)n * 4);
-  pk->c_rd = (uint32_t*)w;
-  w += align_up((size_t)n * 4);
-  pk->s_seg = (int*)w;
-  w += align_up((size_t)(d.Pp + 1) * 4);
-  pk->c_seg = (int*)w;
-  w += align_up((size_t)(d.nb + 1) * 4);
-  pk->c_kinv = (int*)w;
-  w += align_up((size_t)d.nb * 4);
-  return (size_t)(w - b);
-}
-
 struct Ws {
   int* iperm;       // [P]
   int* poscnt;      // [Pp + 1]
@@ -379,8 +325,6 @@ size_t ws_carve(char* b, int64_t n, int32_t P, const Dims& d, Ws* ws) {
   w += ws->cub_bytes;
   return (size_t)(w - b);
 }
-
-bool n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
 
 }  // namespace
 

@@ -808,6 +808,153 @@ def calibrate(obs, S, C, rounds=2, ridge_s=0.0, ridge_c=0.0, fit=("scale", "shif
 
 
 @dataclass
+class BootstrapResult:
+    std_S: torch.Tensor                 # (R, 1, I, J) spread of the refitted S over the replicates
+    std_C: torch.Tensor                 # (R, K)       ... of the refitted C
+    mean_S: torch.Tensor                # (R, 1, I, J) their means (mean - start: the fit's bias)
+    mean_C: torch.Tensor                # (R, K)
+    std_map: Optional[torch.Tensor]     # (K, 1, I, J) spread of T_hat, gauge free (map_std=True)
+    nll: torch.Tensor                   # (n,) fp64, CPU: every replicate's NLL at its refitted point
+    nll_observed: float                 # the NLL of obs at the point the same recipe gives on obs
+    p_fit: float                        # (1 + #{nll_b >= nll_observed}) / (n + 1)
+    n: int
+    invalid: int                        # readings left undrawn (log model, T_hat + offset <= 0)
+
+
+BOOT_REFIT = ("C", "S")
+
+
+def check_bootstrap(n, refit, rounds, ridge_s, ridge_c, max_steps, loss):
+    """Validate the bootstrap arguments (before anything touches a device).
+    -> (n, refit as a tuple, rounds)."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: there is nothing to draw from')
+    if int(n) < 2:
+        raise ValueError("a spread needs n >= 2 replicates, got %r" % (n,))
+    refit = (refit,) if isinstance(refit, str) else tuple(refit)
+    if not refit or any(b not in BOOT_REFIT for b in refit):
+        raise ValueError("refit must name one or both of %s, got %r" % (list(BOOT_REFIT), refit))
+    if int(rounds) < 1:
+        raise ValueError("rounds must be >= 1, got %r" % (rounds,))
+    if not float(ridge_s) >= 0.0 or not float(ridge_c) >= 0.0:
+        raise ValueError("the bootstrap ridges must be >= 0, got %r, %r" % (ridge_s, ridge_c))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be >= 1, got %r" % (max_steps,))
+    return int(n), refit, int(rounds)
+
+
+class Welford:
+    """Running mean and sum of squared deviations (M2) of equally shaped tensors, in fp64 on the
+    tensors' device: add(x) per sample; mean, and std() = sqrt(M2 / (count - 1)), the sample
+    standard deviation (the bootstrap's standard error).  No sample is kept."""
+
+    def __init__(self):
+        self.count, self.mean, self.m2 = 0, None, None
+
+    def add(self, x):
+        x = x.detach().double()
+        if self.mean is None:
+            self.mean, self.m2 = torch.zeros_like(x), torch.zeros_like(x)
+        self.count += 1
+        d = x - self.mean
+        self.mean += d / self.count
+        self.m2 += d * (x - self.mean)
+
+    def std(self):
+        return (self.m2 / (self.count - 1)).sqrt()
+
+
+def scale_gauge(S, C, norms):
+    """(S, C) (R, P), (R, K) rescaled per component so that |c_r|_2 = norms[r] (s_r inversely):
+    the map S^T C is unchanged.  A component whose c_r is 0 is left as it is."""
+    cur = torch.linalg.vector_norm(C.double(), dim=1)
+    a = torch.where(cur > 0, norms.double() / cur, torch.ones_like(cur))
+    a = torch.where(a > 0, a, torch.ones_like(a))
+    return ((S.double() / a[:, None]).to(S.dtype), (C.double() * a[:, None]).to(C.dtype))
+
+
+def _refit_pos(obs, S_pos, C, R, refit, rounds, ridge_s, ridge_c, max_steps, project_s):
+    """The bootstrap's refit recipe on a position-order S (Pp, RP) and a device C (R, K): `rounds`
+    times fit_C then fit_S (those of `refit`), calibrate's own calls, each from the current point;
+    then the NLL there (model_nll's walk).  -> (S_pos, C, nll (1,) fp64), all on the device:
+    nothing is read back (fit_C runs with sync_every = 0)."""
+    kind_s, project_s = _defaults(obs, None, project_s)
+    kind_c, _ = _defaults(obs, None, True)
+    for _ in range(rounds):
+        if "C" in refit:
+            C = _fit_c_pos(obs, S_pos, C, R, kind_c, ridge_c, max_steps, 1e-5, 1e-3, True,
+                           sync_every=0)[0]
+        if "S" in refit:
+            S_pos = _fit_s_pos(obs, S_pos, C, R, kind_s, ridge_s, max_steps, 1e-5, 1e-3,
+                               project_s)[0]
+    f = _fit_noise_pos(obs, S_pos, C, R, "observed", 1, (0.0, 0.0), (0.0, 0.0), 1, 1e-6, 0.0,
+                       sync_every=0, iterate=False)[1]
+    return S_pos, C, f[1:2]
+
+
+def bootstrap(obs, S, C, n=32, seed=0, refit=("C", "S"), rounds=1, ridge_s=0.0, ridge_c=0.0,
+              max_steps=30, project_s=None, map_std=False):
+    """Parametric bootstrap of the fit at (S, C): the joint uncertainty of S and C, and whether
+    the whole fit is consistent with its data.
+
+    confidence, fit_C's std_C and check_fit are conditional on the other factor and bound the joint
+    uncertainty from below; model_nll is one number without a scale.  Here n replicates of the
+    readings are drawn from the fitted model over the same sampling pattern
+    (obs.resample(S, C, seed, b), b = 0 .. n - 1: the very P_b the likelihood evaluates, at the
+    observed cells only), and every replicate is refitted by the recipe
+        `rounds` times from (S, C):  fit_C(C_init=...) if "C" in refit, then fit_S(S_init=...) if
+        "S" in refit
+    -- calibrate's own calls, with ridge_c, ridge_s, max_steps and project_s meaning what they
+    mean there.  The same recipe runs once on obs itself for nll_observed.  The NLLs are model_nll
+    of the refitted points, and p_fit = (1 + #{nll_b >= nll_observed}) / (n + 1): small when the
+    data are less likely than data from the model are (1 / (n + 1) is the smallest value).
+    The spread is accumulated by Welford's update in fp64 on the device (sample standard deviation
+    over the n replicates); one replicate's Observations is held at a time, and the host waits
+    once per replicate, to read its NLL.  The model sees only S^T C, so before a replicate enters
+    the sums its scale gauge is fixed: each component is rescaled so that |c_r|_2 equals the
+    start's (s_r inversely; the reference's ColumnNormalization idea).  The refit starts inside
+    the start's basin, so components are not re-matched by permutation.  std_map, the spread of
+    T_hat itself, needs no gauge; it is the only K x P output and is opt-in (map_std=True).
+    With refit=("S",) and ridge_s = 0, std_S estimates what confidence(kind="expected").std_S
+    bounds.  Not done here: refitting the quantiser (fit_noise), the Adam solver as the refit,
+    the generator / DIP modes, sharded solvers.
+    obs: the Observations; S (R,1,I,J) or (R,I,J), C (R,K).  Returns BootstrapResult(std_S, std_C,
+    mean_S, mean_C, std_map, nll (n,), nll_observed, p_fit, n, invalid).  Raises ValueError for
+    n < 2, an empty refit or an unknown name in it, rounds < 1, negative ridges, max_steps < 1,
+    obs.loss == "squared" or shapes that do not match obs, before any GPU call."""
+    n, refit, rounds = check_bootstrap(n, refit, rounds, ridge_s, ridge_c, max_steps,
+                                       getattr(obs, "loss", None))
+    R, _ = Observations.check_resample(obs.loss, obs.K, obs.I, obs.J, S, C, seed, 0)
+    S0 = _dev(S.detach().to(torch.float32)).reshape(R, obs.P).contiguous()
+    S_pos0, C0 = _inputs(obs, S0, C, R)
+    norms = torch.linalg.vector_norm(C0.double(), dim=1)
+    recipe = (R, refit, rounds, ridge_s, ridge_c, max_steps, project_s)
+    nll_observed = float(_refit_pos(obs, S_pos0, C0, *recipe)[2])
+    acc_s, acc_c, acc_t = Welford(), Welford(), Welford()
+    nll = torch.empty(n, dtype=torch.float64)
+    invalid = torch.zeros(1, dtype=torch.int32, device=S_pos0.device)
+    for b in range(n):
+        rep = obs.resample(S0, C0, seed, b)
+        S_pos, Cb, f = _refit_pos(rep, S_pos0, C0, *recipe)
+        invalid += rep.invalid
+        Sb, Cb = scale_gauge(obs.to_pixels(S_pos, R), Cb, norms)
+        acc_s.add(Sb)
+        acc_c.add(Cb)
+        if map_std:
+            from ._model import get_tensor
+            acc_t.add(get_tensor(Sb.reshape(R, 1, obs.I, obs.J), Cb))
+        nll[b] = float(f)  # the one wait of this replicate
+        del rep
+    shape_s = (R, 1, obs.I, obs.J)
+    return BootstrapResult(
+        std_S=acc_s.std().float().reshape(shape_s), std_C=acc_c.std().float(),
+        mean_S=acc_s.mean.float().reshape(shape_s), mean_C=acc_c.mean.float(),
+        std_map=acc_t.std().float().reshape(obs.K, 1, obs.I, obs.J) if map_std else None,
+        nll=nll, nll_observed=nll_observed,
+        p_fit=(1 + int((nll >= nll_observed).sum())) / (n + 1), n=n, invalid=int(invalid.item()))
+
+
+@dataclass
 class FitSSmoothResult:
     S: Optional[torch.Tensor]           # (R, 1, I, J), pixel order (None in SolveResult.polish_smooth)
     nll: float                          # -sum log P at S over the observed entries

@@ -354,6 +354,73 @@ class Observations:
                 new._fill(rowfmt, new.desc, new.s_entries, new.c_entries)
         return new
 
+    @staticmethod
+    def check_resample(loss, K, I, J, S, C, seed=0, replicate=0):
+        """Host-side checks of resample's arguments, before any device call: a likelihood, S
+        (R,1,I,J) or (R,I,J) (or (R,I J)), C (R,K), 1 <= R <= 16, seed in [-2^63, 2^64),
+        0 <= replicate < 2^31.  -> (R, seed as a signed 64-bit value).  Raises ValueError."""
+        if loss == "squared":
+            raise ValueError('loss="squared" is not a likelihood: there is nothing to draw from')
+        for name, t in (("S", S), ("C", C)):
+            if not isinstance(t, torch.Tensor) or t.dim() < 2:
+                raise ValueError("%s must be a tensor of at least two dimensions" % name)
+        R = int(S.shape[0])
+        if not 1 <= R <= _lib.QSC_MAX_R:
+            raise ValueError("rank R must be in [1, %d], got %d" % (_lib.QSC_MAX_R, R))
+        if tuple(S.shape) not in ((R, 1, I, J), (R, I, J), (R, I * J)):
+            raise ValueError("S must be (R, 1, %d, %d) or (R, %d, %d), got %s"
+                             % (I, J, I, J, tuple(S.shape)))
+        if tuple(C.shape) != (R, K):
+            raise ValueError("C must be (%d, %d), got %s" % (R, K, tuple(C.shape)))
+        seed, replicate = int(seed), int(replicate)
+        if not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 bits, got %r" % (seed,))
+        if not 0 <= replicate < 2 ** 31:
+            raise ValueError("replicate must be in [0, 2^31), got %r" % (replicate,))
+        return R, (seed - 2 ** 64 if seed >= 2 ** 63 else seed)
+
+    def resample(self, S, C, seed=0, replicate=0):
+        """New readings drawn from the model at (S, C) over the same sampling pattern: the draw of
+        the parametric bootstrap (fits.bootstrap), of simulation from a truth and of coverage
+        checks.  Every observed reading is replaced by a code drawn from the very P_b the
+        likelihood evaluates at its cell (include/qsc.h, qsc_draw_codes / qsc_draw_readings, has
+        the rule); the generator is counter based, so a reading's draw depends only on (seed,
+        replicate, bin, pixel, occurrence of the cell) -- not on the tile, pixel order, schedule,
+        entry format or dense / readings input.
+        The result is a new Observations: it shares perm, tile, counts, the width / offset / bin
+        order tables and the model with this one (they depend on the pattern, not the codes) and
+        owns its codes (or sorted readings), descriptor and entry arrays, filled in the row
+        format this object has (the schedule is re-run: row residues depend on the codes).  This
+        object is left untouched, so hipGraphs captured on it stay valid.  `result.invalid` is a
+        device int32 counter of the readings left as they were because T_hat + offset <= 0 (log
+        model).  S (R,1,I,J) or (R,I,J), C (R,K).  Raises ValueError for shapes that do not
+        match, loss="squared", or seed / replicate out of range, before any device call."""
+        import copy
+        R, seed64 = self.check_resample(self.loss, self.K, self.I, self.J, S, C, seed, replicate)
+        Cd = _dev(C.detach().to(torch.float32)).reshape(R, self.K).contiguous()
+        Sd = _dev(S.detach().to(torch.float32)).reshape(R, self.P).contiguous()
+        new = copy.copy(self)
+        new.invalid = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.codes is None:
+            S_pos = self.to_positions(Sd)
+            new._packed = torch.empty_like(self._packed)
+            _lib.call("qsc_draw_readings", _lib.ptr(self._packed), self._packed.numel(), self._n,
+                      self.desc, _lib.ptr(self.perm), self.model, R, _lib.ptr(S_pos), _lib.ptr(Cd),
+                      seed64, int(replicate), _lib.ptr(new._packed), _lib.ptr(new.invalid),
+                      _lib.stream())
+        else:
+            new.codes = torch.empty_like(self.codes)
+            _lib.call("qsc_draw_codes", _lib.ptr(self.codes), self.K, self.P, self.model, R,
+                      _lib.ptr(Sd), _lib.ptr(Cd), seed64, int(replicate), _lib.ptr(new.codes),
+                      _lib.ptr(new.invalid), _lib.stream())
+        new.desc = _lib.QscObsDesc()
+        ctypes_copy(new.desc, self.desc)
+        new.s_entries = torch.empty_like(self.s_entries)
+        new.c_entries = torch.empty_like(self.c_entries)
+        new._engines, new._code_field = 0, None
+        new._fill(self.desc.rowfmt)
+        return new
+
     def signed_rows_ok(self, R):
         if os.environ.get("QSC_SIGNED_ROWS", "1") == "0":  # A/B switch (tuning runs)
             return False

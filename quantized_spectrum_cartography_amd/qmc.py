@@ -24,8 +24,8 @@ from . import _lib
 from ._model import _dev, map_nmse
 # the post-solve estimators live in fits.py; qmc.fit_S etc. stay the user-facing spellings
 from .fits import (  # noqa: F401
-    DESIGN_CRITERIA, INFO_KINDS, CalibrateResult, CheckResult, ConfidenceResult, DesignResult,
-    FitCResult,
+    DESIGN_CRITERIA, INFO_KINDS, BootstrapResult, CalibrateResult, CheckResult, ConfidenceResult,
+    DesignResult, FitCResult, bootstrap, check_bootstrap,
     FitNoiseResult, FitSResult, FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos,
     _fit_s_smooth_pos, _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_design,
     check_fit, check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
