@@ -1131,6 +1131,64 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
                               int32_t replicate, void* packed_out, int32_t* invalid,
                               void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Subsets of packed observations (qsc_obs_select.hip): narrow, split and read back what is
+ * already packed, on the device.  Not in the reference.  Behind Observations.select / split /
+ * folds / readings.
+ *   THE KEEP RULE.  Reading (k, p, j_occ) of the parent (bin k, pixel p = i J + j in natural
+ *   order, j_occ its occurrence number in its cell as the draws count it: 0 for dense codes) is
+ *   kept iff
+ *       keep_pixel[p] != 0  and  keep_bin[k] != 0  and  ((lo <= u24 < hi) != invert)
+ *     keep_pixel  uint8[P], natural pixel order; NULL = all ones
+ *     keep_bin    uint8[K]; NULL = all ones
+ *     u24         = x0 >> 8, (x0, ..) = Philox4x32-10(counter (k, p, j_occ, 0x80000000),
+ *                   key (seed & 0xFFFFFFFF, seed >> 32)): the generator of the draws above, on
+ *                   a stream they never use (their word 3 is a replicate < 2^31)
+ *     0 <= lo <= hi <= 2^24, invert 0 or 1;  lo = 0, hi = 2^24, invert = 0 switches the range
+ *                   rule off (u24 < 2^24 always; no Philox is then evaluated)
+ *   All arithmetic is on integers: there is no rounding, and a host reference is exact.  The rule
+ *   reads nothing of the packing: a reading is kept or not whatever the tile, pixel order, list
+ *   schedule, entry format and dense / readings input.  Complementary ranges (invert) partition
+ *   the parent exactly; the ranges [(f << 24) / n, ((f + 1) << 24) / n) of f = 0 .. n - 1 tile
+ *   [0, 2^24) and partition it into n folds.
+ * All calls: asynchronous on `stream`, no allocation, integer atomics for *kept only (positions
+ * of exported readings are decided by scans: the output bytes are a function of the input).
+ * QSC_EINVAL for a null pointer, a shape out of range, a range outside 0 <= lo <= hi <= 2^24, an
+ * invert other than 0 / 1, a workspace too small or a layout mismatch.
+ * ------------------------------------------------------------------------------------- */
+#define QSC_EXPORT_CHUNK_CODES 4096    /* cells of codes[K][P] (flat) per workgroup */
+#define QSC_EXPORT_CHUNK_READINGS 1024 /* sorted readings per workgroup */
+/* Dense: out[k][p] = codes[k][p] where the cell is observed and kept, 0xFF elsewhere (out is
+ * another array).  *kept (device int64, zeroed by the caller) += the number of kept cells.
+ * 16-byte loads when P % 16 == 0 and both arrays are 16-byte aligned, byte loads otherwise; the
+ * observed cells of a chunk are compacted in LDS first, so an unobserved cell costs no Philox. */
+QSC_API int qsc_select_codes(const uint8_t* codes, int32_t K, int32_t P, const uint8_t* keep_pixel,
+                             const uint8_t* keep_bin, int64_t seed, int32_t lo, int32_t hi,
+                             int32_t invert, uint8_t* out, int64_t* kept, void* stream);
+/* Workspace of either export below over `entries` entries (K P cells, or n readings); 0 when out
+ * of range.  Sized for chunks of QSC_EXPORT_CHUNK_READINGS: exact for the readings form, an upper
+ * bound (about four times what it uses) for the codes form, whose chunks are four times as large. */
+QSC_API size_t qsc_export_workspace_bytes(int64_t entries);
+/* The kept cells of a dense codes[K][P] as three lists (int32 k, int32 p, uint8 code), ascending
+ * (k, p); *n_out (device int64) = their number.  The lists need room for every observed cell
+ * (the parent's nnz).  A stable stream compaction: kept count per chunk, one exclusive scan of the
+ * chunk counts, the rule again with an in-chunk ballot / popcount scan and the scatter. */
+QSC_API int qsc_export_codes(const uint8_t* codes, int32_t K, int32_t P, const uint8_t* keep_pixel,
+                             const uint8_t* keep_bin, int64_t seed, int32_t lo, int32_t hi,
+                             int32_t invert, int32_t* k_out, int32_t* p_out, uint8_t* code_out,
+                             int64_t* n_out, void* ws, size_t ws_bytes, void* stream);
+/* The kept readings of a list packing (`packed`, n = d->nnz readings, perm[Pp] as
+ * qsc_obs_readings_layout took them), read from the S-format sorted array: the position from the
+ * segment table, p = perm[position], k and the code from the reading, j_occ by looking back along
+ * the run of equal k inside the position's own segment (a run may cross a chunk boundary).  Order:
+ * (position, k, occurrence).  The lists need room for n readings.  The same three steps. */
+QSC_API int qsc_export_readings(const void* packed, size_t packed_bytes, int64_t n,
+                                const qsc_obs_desc* d, const int32_t* perm,
+                                const uint8_t* keep_pixel, const uint8_t* keep_bin, int64_t seed,
+                                int32_t lo, int32_t hi, int32_t invert, int32_t* k_out,
+                                int32_t* p_out, uint8_t* code_out, int64_t* n_out, void* ws,
+                                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // qsc_obs_readings.cuh — the caller-kept sorted readings (`packed`) of the list packing: their
 // shapes, their carving and the search of a segment table.  Shared by qsc_obs_readings.hip (which
-// writes them and fills the entry formats from them) and qsc_draw.hip (which redraws their codes).
+// writes them and fills the entry formats from them), qsc_draw.hip (which redraws their codes) and
+// qsc_obs_select.hip (which exports the kept ones as lists).
 //
 // A sorted reading is  idx | code << 24  (idx = k or qlocal < 2^24, the wide format's own bound).
 #pragma once

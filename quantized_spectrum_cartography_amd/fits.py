@@ -1,5 +1,6 @@
 """The post-solve estimators (not in the reference): confidence, design, check_fit, the Newton
-fits fit_S, fit_C, fit_S_smooth and fit_noise, model_nll, calibrate, and the stage of solve() that runs them on its
+fits fit_S, fit_C, fit_S_smooth and fit_noise, model_nll, calibrate, bootstrap, cross_validate,
+and the stage of solve() that runs them on its
 result (check_post_solve, post_solve).  Every public function validates its arguments before
 anything touches a device; the `_*_pos` drivers take a position-order S (Pp, RP) and device
 tensors.  qmc re-exports the names: qmc.fit_S etc. stay the user-facing spellings.
@@ -742,6 +743,54 @@ def model_nll(obs, S, C):
     _, f, _, _, _ = _fit_noise_pos(obs, S_pos, Cd, R, "observed", 1, (0.0, 0.0), (0.0, 0.0), 1,
                                    1e-6, 0.0, iterate=False)
     return float(f[1])
+
+
+@dataclass
+class CrossValidateResult:
+    nll: List[float]        # per fold: model_nll(test, S, C) / test.nnz at the fit on train
+    mean: float             # their mean
+    stderr: float           # standard error of the mean over the folds
+    n_test: List[int]       # readings of every test part
+    n_train: List[int]      # readings of every train part
+
+
+def check_cross_validate(loss, fit, folds=5, seed=0):
+    """Host-side checks of cross_validate's arguments, before any device call.  -> None."""
+    if loss == "squared":
+        raise ValueError('loss="squared" is not a likelihood: there is no held-out NLL to score')
+    if not callable(fit):
+        raise ValueError("fit must be a callable: train Observations -> (S, C)")
+    Observations.check_split(seed=seed, n=0 if folds is None else folds)
+
+
+def cross_validate(obs, fit, folds=5, seed=0):
+    """K-fold cross-validation of any fitting recipe by held-out likelihood.  obs.folds(folds,
+    seed) splits the packed readings on the device (every reading is in exactly one test part);
+    for each fold S, C = fit(train) -- any callable that returns (S, C) or an object with .S and
+    .C -- and the score is model_nll(test, S, C) / test.nnz, the held-out NLL per reading.
+    -> CrossValidateResult (per-fold scores, their mean, the standard error over folds, sizes).
+    The intended uses, a grid over the smoothness weight and over the rank:
+        for w in (0.0, 0.1, 1.0):
+            cv[w] = cross_validate(obs, lambda tr: solve(None, None, b, sigma, R=R, obs=tr,
+                                                         smooth=w, max_iter=200))
+        for R in (2, 3, 4):
+            cv[R] = cross_validate(obs, lambda tr: solve(None, None, b, sigma, R=R, obs=tr))
+    and the one with the smallest mean wins (differences inside stderr are ties; the folds share
+    a seed, so two recipes are scored on the same parts and may be compared fold by fold).
+    Raises ValueError for loss="squared" (no likelihood), folds outside [2, 65536] or a seed out
+    of range, before any device call, and when a part is empty."""
+    check_cross_validate(getattr(obs, "loss", None), fit, folds, seed)
+    nll, n_test, n_train = [], [], []
+    for train, test in obs.folds(folds, seed):
+        out = fit(train)
+        S, C = (out.S, out.C) if hasattr(out, "S") and hasattr(out, "C") else out
+        nll.append(model_nll(test, S, C) / test.nnz)
+        n_test.append(test.nnz)
+        n_train.append(train.nnz)
+    mean = sum(nll) / len(nll)
+    var = sum((v - mean) ** 2 for v in nll) / (len(nll) - 1)
+    return CrossValidateResult(nll=nll, mean=mean, stderr=math.sqrt(var / len(nll)),
+                               n_test=n_test, n_train=n_train)
 
 
 @dataclass

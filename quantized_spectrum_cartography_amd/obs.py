@@ -75,6 +75,31 @@ def neighbor_table(perm, I, J):
     return nbr
 
 
+class _Folds:
+    """Observations.folds: fold f -> (train, test), built on access."""
+
+    def __init__(self, obs, n, seed64):
+        self.obs, self.n, self.seed64 = obs, n, seed64
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, f):
+        if isinstance(f, bool) or not isinstance(f, int):
+            raise TypeError("fold index must be an int")
+        if f < 0:
+            f += self.n
+        if not 0 <= f < self.n:
+            raise IndexError("fold %d of %d" % (f, self.n))
+        o = self.obs
+        lo, hi = o.fold_range(f, self.n)
+        return (o._subset(None, None, self.seed64, lo, hi, 1, o.perm),
+                o._subset(None, None, self.seed64, lo, hi, 0, o.perm))
+
+    def __iter__(self):
+        return (self[f] for f in range(self.n))
+
+
 class Observations:
     """Packed observations of one K-slab.
 
@@ -112,6 +137,11 @@ class Observations:
         if nbad:
             raise ValueError("%d observed entries have a code outside [0, %d) or a sampling "
                              "weight other than 0/1" % (nbad, nbins))
+        self._pack_codes(codes, perm, count_hook, PT, nbins, R_hint)
+
+    def _pack_codes(self, codes, perm, count_hook, PT, nbins, R_hint):
+        """Construction from the dense codes on (after _setup): count, order, layout, fill."""
+        K, P, dev = self.K, self.P, self.device
         self.codes = codes
         s = _lib.stream()
         cnt = torch.empty(P, dtype=torch.int32, device=dev)
@@ -253,6 +283,13 @@ class Observations:
         cd = _dev(code)
         cd = (cd if cd.dtype == torch.uint8 else
               cd.to(torch.int64).clamp(-1, 1 << 20).to(torch.int32)).contiguous()
+        self._pack_readings(kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint)
+        return self
+
+    def _pack_readings(self, kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint):
+        """from_readings from the device lists on (after _setup): int32 k, int32 p = i J + j,
+        uint8 or int32 code, n of each: count, order, layout (two sorts), fill."""
+        K, I, J, P, dev = self.K, self.I, self.J, self.P, self.device
         cb = 1 if cd.dtype == torch.uint8 else 4
         s = _lib.stream()
         cnt = torch.empty(P, dtype=torch.int32, device=dev)
@@ -289,7 +326,6 @@ class Observations:
                              "reading needs a position" % (int(desc.nnz), n))
         self.max_repeat = int(rep.value)
         self._finish(desc, R_hint)
-        return self
 
     def _fill(self, rowfmt, desc=None, s_entries=None, c_entries=None):
         """Pack the entries in format `rowfmt` into (desc, s_entries, c_entries) (default: this
@@ -420,6 +456,165 @@ class Observations:
         new._engines, new._code_field = 0, None
         new._fill(self.desc.rowfmt)
         return new
+
+    # ---- subsets: select, split, folds, readings (include/qsc.h, the keep rule) ------------
+    RANGE = 1 << 24  # the keep rule's u24 lies in [0, RANGE)
+
+    @staticmethod
+    def frac_range(frac):
+        """hi of the held-out range [0, hi) of split(frac): round(frac 2^24) in [1, 2^24 - 1]."""
+        return min(max(int(round(float(frac) * Observations.RANGE)), 1), Observations.RANGE - 1)
+
+    @staticmethod
+    def fold_range(f, n):
+        """(lo, hi) of the test range of fold f of n: the n ranges tile [0, 2^24)."""
+        return (int(f) << 24) // int(n), ((int(f) + 1) << 24) // int(n)
+
+    @staticmethod
+    def check_select(K, I, J, pixels=None, bins=None, perm="keep"):
+        """Host-side checks of select's arguments, before any device call: pixels an (I, J) bool
+        tensor or None, bins a (K,) bool tensor or None, perm "keep" or "fresh".  Raises
+        ValueError."""
+        for name, t, shape in (("pixels", pixels, (I, J)), ("bins", bins, (K,))):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.bool:
+                raise ValueError("%s must be a bool tensor, got %s"
+                                 % (name, t.dtype if isinstance(t, torch.Tensor) else type(t)))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+        if perm not in ("keep", "fresh"):
+            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+
+    @staticmethod
+    def check_split(frac=None, seed=0, n=None, perm="keep"):
+        """Host-side checks of split's (frac) and folds' (n) arguments, before any device call:
+        0 < frac < 1, 2 <= n <= 65536, seed in [-2^63, 2^64) (resample's range), perm "keep" or
+        "fresh".  -> seed as a signed 64-bit value.  Raises ValueError."""
+        if frac is not None:
+            try:
+                ok = 0.0 < float(frac) < 1.0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("the held-out fraction must be in (0, 1), got %r" % (frac,))
+        if n is not None:
+            if isinstance(n, bool) or not isinstance(n, int) or not 2 <= n <= 65536:
+                raise ValueError("the number of folds must be an int in [2, 65536], got %r" % (n,))
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError("seed must be an int, got %r" % (seed,))
+        if not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 bits, got %r" % (seed,))
+        if perm not in ("keep", "fresh"):
+            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+        return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+    def _child(self):
+        """A new Observations with this one's shape, model, loss, tile, R_hint and schedule flag
+        and nothing packed yet (what _setup leaves)."""
+        new = Observations.__new__(Observations)
+        for a in ("K", "I", "J", "P", "Pp", "schedule", "model", "loss", "log_model", "noise_std",
+                  "offset", "bin_boundaries", "device"):
+            setattr(new, a, getattr(self, a))
+        new.R_hint = getattr(self, "R_hint", 8)
+        return new
+
+    def _masks(self, pixels, bins):
+        kp = None if pixels is None else _dev(pixels.reshape(self.P)).to(torch.uint8).contiguous()
+        kb = None if bins is None else _dev(bins.reshape(self.K)).to(torch.uint8).contiguous()
+        return kp, kb
+
+    def _export(self, kp, kb, seed64, lo, hi, invert):
+        """The kept readings as device lists (int32 k, int32 p, uint8 code) and their number
+        (read back): qsc_export_codes (ascending (k, p)) or qsc_export_readings ((position, k,
+        occurrence))."""
+        dev, nnz = self.device, self.nnz
+        k = torch.empty(nnz, dtype=torch.int32, device=dev)
+        p = torch.empty(nnz, dtype=torch.int32, device=dev)
+        c = torch.empty(nnz, dtype=torch.uint8, device=dev)
+        m = torch.zeros(1, dtype=torch.int64, device=dev)
+        entries = self.K * self.P if self.codes is not None else self._n
+        wb = _lib.lib().qsc_export_workspace_bytes(entries)
+        if wb == 0:
+            raise ValueError("%d entries are out of the export's range" % entries)
+        ws = _ws(wb, dev)
+        rule = (_lib.ptr(kp), _lib.ptr(kb), seed64, lo, hi, invert, _lib.ptr(k), _lib.ptr(p),
+                _lib.ptr(c), _lib.ptr(m), _lib.ptr(ws), ws.numel(), _lib.stream())
+        if self.codes is not None:
+            _lib.call("qsc_export_codes", _lib.ptr(self.codes), self.K, self.P, *rule)
+        else:
+            _lib.call("qsc_export_readings", _lib.ptr(self._packed), self._packed.numel(), self._n,
+                      self.desc, _lib.ptr(self.perm), *rule)
+        return k, p, c, int(m.item())
+
+    def _subset(self, kp, kb, seed64, lo, hi, invert, perm):
+        """The Observations over the readings the rule keeps; perm: a (Pp,) pixel order, or None
+        for the order by the new counts."""
+        new = self._child()
+        PT, nbins = int(self.desc.PT), int(self.desc.nbins)
+        if self.codes is not None:
+            codes = torch.empty_like(self.codes)
+            kept = torch.zeros(1, dtype=torch.int64, device=self.device)
+            _lib.call("qsc_select_codes", _lib.ptr(self.codes), self.K, self.P, _lib.ptr(kp),
+                      _lib.ptr(kb), seed64, lo, hi, invert, _lib.ptr(codes), _lib.ptr(kept),
+                      _lib.stream())
+            if not int(kept.item()):
+                raise ValueError("the selection leaves no reading")
+            new._pack_codes(codes, perm, None, PT, nbins, new.R_hint)
+        else:
+            k, p, c, m = self._export(kp, kb, seed64, lo, hi, invert)
+            if not m:
+                raise ValueError("the selection leaves no reading")
+            new._pack_readings(k[:m], p[:m], c[:m], m, perm, None, PT, nbins, new.R_hint)
+        return new
+
+    def select(self, pixels=None, bins=None, perm="keep"):
+        """The readings of the kept pixels and bins as a new Observations with this one's model,
+        loss, tile, R_hint and schedule flag: pixels an (I, J) bool mask of the pixels to keep,
+        bins a (K,) bool mask (None: all) -- e.g. obs.select(pixels=~check.flagged(...)) drops the
+        sensors check_fit flags, also where the raw data are gone (resample, with_model,
+        calibrate results).  perm="keep" keeps this object's pixel order, so that position-order
+        S, information blocks and captured state stay compatible and the result is a valid
+        obs_holdout partner; perm="fresh" orders the pixels by the new counts.  On the device
+        (include/qsc.h, the keep rule): dense codes are masked by qsc_select_codes and packed by
+        the constructor's own count / layout / fill; a list packing is exported by
+        qsc_export_readings and packed as from_readings packs (one re-sort).  This object is left
+        untouched.  Raises ValueError for masks of another shape or dtype (before any device
+        call) and when no reading is left."""
+        self.check_select(self.K, self.I, self.J, pixels, bins, perm)
+        kp, kb = self._masks(pixels, bins)
+        return self._subset(kp, kb, 0, 0, self.RANGE, 0, self.perm if perm == "keep" else None)
+
+    def split(self, frac, seed=0, perm="keep"):
+        """(fit, held): a seeded random split of the readings, `held` about the fraction `frac`
+        of them.  A reading goes to `held` iff its u24 (the keep rule's counter-based 24-bit
+        number, a function of (seed, bin, pixel, occurrence of the cell) alone) lies in
+        [0, round(frac 2^24)) (clamped to [1, 2^24 - 1]), to `fit` otherwise: the halves partition
+        this object exactly, and the same reading falls on the same side whatever the tile, pixel
+        order, schedule, row format and dense / readings input.  perm="keep": both halves in this
+        object's pixel order; "fresh": `fit` ordered by its own counts and `held` packed with
+        fit.perm.  Either way `held` is a valid obs_holdout partner of `fit`."""
+        seed64 = self.check_split(frac=float("nan") if frac is None else frac, seed=seed, perm=perm)
+        h = self.frac_range(frac)
+        fit = self._subset(None, None, seed64, 0, h, 1, self.perm if perm == "keep" else None)
+        return fit, self._subset(None, None, seed64, 0, h, 0, fit.perm)
+
+    def folds(self, n, seed=0):
+        """A sequence of n (train, test) pairs, each built when it is asked for (and not kept):
+        fold f's test part holds the readings with u24 in [(f << 24) // n, ((f + 1) << 24) // n),
+        its train part the others; the n test parts partition this object.  All in this object's
+        pixel order.  2 <= n <= 65536."""
+        return _Folds(self, n, self.check_split(seed=seed, n=0 if n is None else n))
+
+    def readings(self):
+        """(k, i, j, code): every packed reading as device tensors (int32, int32, int32, uint8),
+        in ascending (k, pixel) order for dense input and (position, k, occurrence) order for a
+        list packing.  Observations.from_readings(*obs.readings(), shape, ..., perm=obs.perm,
+        tile=obs.desc.PT) rebuilds the packing bit for bit."""
+        k, p, c, m = self._export(None, None, 0, 0, self.RANGE, 0)
+        k, p, c = k[:m], p[:m], c[:m]
+        i = torch.div(p, self.J, rounding_mode="floor")
+        return k, i, p - i * self.J, c
 
     def signed_rows_ok(self, R):
         if os.environ.get("QSC_SIGNED_ROWS", "1") == "0":  # A/B switch (tuning runs)

@@ -25,7 +25,8 @@ from ._model import _dev, map_nmse
 # the post-solve estimators live in fits.py; qmc.fit_S etc. stay the user-facing spellings
 from .fits import (  # noqa: F401
     DESIGN_CRITERIA, INFO_KINDS, BootstrapResult, CalibrateResult, CheckResult, ConfidenceResult,
-    DesignResult, FitCResult, bootstrap, check_bootstrap,
+    CrossValidateResult, DesignResult, FitCResult, bootstrap, check_bootstrap,
+    check_cross_validate, cross_validate,
     FitNoiseResult, FitSResult, FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos,
     _fit_s_smooth_pos, _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_design,
     check_fit, check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
@@ -59,6 +60,10 @@ class SolveResult:
     # solve(calibrate=n): the qmc.calibrate run on S, C (without them; .obs is the calibrated one)
     calibration: Optional["CalibrateResult"] = None
     check: Optional["CheckResult"] = None  # solve(check=True): qmc.check_fit at the returned S, C
+    # solve(obs=, holdout=) and solve_readings: the packed observations the fit ran on, and the
+    # held-out ones it early-stopped on (None without a holdout)
+    obs: Optional[Observations] = None
+    obs_holdout: Optional[Observations] = None
 
 
 class FreeSSolver(AlternatingSolver):
@@ -275,7 +280,10 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
     `check_every` iterations their NLL at the current S, C is evaluated (fused HIP S-pass on
     the held-out set, same pixel order), and the run stops once it has not improved for
     `patience` checks, returning the S, C of the best check (result.best_iter, .holdout_nll).
-    With ~6 one-bit samples per pixel (C2) the unregularised free-S MLE over-fits: the map
+    With obs= the packed readings are split on the device by obs.split(holdout, holdout_seed)
+    (a counter-based split: other entries than the Y, Wx path's host draw holds out) and the
+    result gains `obs` and `obs_holdout`, the two halves; qmc.cross_validate repeats this over
+    K folds.  With ~6 one-bit samples per pixel (C2) the unregularised free-S MLE over-fits: the map
     NMSE is best after ~50 iterations and grows after.
     smooth > 0 (free S only; not in the reference, whose spatial prior is the generator): adds
     the smoothness prior smooth * R(S) on the loss fields to the cost of both steps, R summed
@@ -376,10 +384,12 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
         R = (S_init.shape[0] if S_init is not None else
              (C_init.shape[0] if C_init is not None else Z_init.shape[0]))
     obs_h = obs_holdout
-    if holdout and generator is None and obs_h is None:
-        if obs is not None:
-            raise ValueError("holdout splits the observations itself: pass Y, Wx, not obs (or "
-                             "split a list of readings with solve_readings)")
+    split_obs = False
+    if holdout and generator is None and obs_h is None and obs is not None:
+        # packed observations are split on the device, in obs's pixel order (obs.split)
+        obs, obs_h = obs.split(float(holdout), holdout_seed)
+        split_obs = True
+    elif holdout and generator is None and obs_h is None:
         Wx_fit, Wx_h = split_holdout(Y, Wx, float(holdout), holdout_seed)
         obs = Observations(Y, Wx_fit, bin_boundaries, noise_std, offset=offset or 0.0,
                            log_model=log_model, tile=tile, R_hint=R, loss=loss)
@@ -398,8 +408,11 @@ def solve(Y, Wx, bin_boundaries, noise_std, R=None, S_init=None, C_init=None, of
                              max_iter, betas, eps, project_c, fuse, project_s, use_graph,
                              int(check_every), int(patience), smooth, smooth_kind, smooth_delta)
         # (on the fitted entries, the held-out ones excluded)
-        return post_solve(res, obs, post, lambda_s, lambda_c, project_s, smooth, smooth_kind,
-                          smooth_delta)
+        res = post_solve(res, obs, post, lambda_s, lambda_c, project_s, smooth, smooth_kind,
+                         smooth_delta)
+        if split_obs:
+            res.obs, res.obs_holdout = obs, obs_h
+        return res
     if generator is None:
         if S_init is None:
             S_init = torch.zeros(R, 1, I, J)
