@@ -1130,6 +1130,17 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
                               int32_t R, const float* S, const float* C, int64_t seed,
                               int32_t replicate, void* packed_out, int32_t* invalid,
                               void* stream);
+/* Listed cells: code[e] = the draw at bin k[e], pixel p[e] (natural index), occurrence occ[e]
+ * (occ NULL: 0), e = 0 .. n - 1, whether the cell is observed or not -- the rule above word for
+ * word, by the same device functions, so that a draw at (k, p, j_occ) is the code qsc_draw_codes /
+ * qsc_draw_readings give the reading (k, p, j_occ).  There is no present code to keep: a reading
+ * nothing is drawn for (log model with t + offset <= 0, counted in *invalid; every P_b zero or
+ * NaN; k or p out of range) gets QSC_UNOBSERVED.  k, p, occ: device int32 lists; S natural planes
+ * [R][P], C [R][K] (qsc_draw_codes' sum).  One thread per query. */
+QSC_API int qsc_draw_list(const int32_t* k, const int32_t* p, const int32_t* occ, int64_t n,
+                          int32_t K, int32_t P, const qsc_model* m, int32_t R, const float* S,
+                          const float* C, int64_t seed, int32_t replicate, uint8_t* code,
+                          int32_t* invalid, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Subsets of packed observations (qsc_obs_select.hip): narrow, split and read back what is
@@ -1188,6 +1199,58 @@ QSC_API int qsc_export_readings(const void* packed, size_t packed_bytes, int64_t
                                 int32_t lo, int32_t hi, int32_t invert, int32_t* k_out,
                                 int32_t* p_out, uint8_t* code_out, int64_t* n_out, void* ws,
                                 size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Growing a list packing (qsc_obs_append.hip): how often a cell has been read, and the append of a
+ * batch of readings without re-sorting the parent.  Not in the reference.  Behind
+ * Observations.occurrences / draw / append.
+ *   Both sort keys of the list packing -- (position, k) and (tile, bin in k order, qlocal) --
+ *   depend on the pixel order alone.  With the parent's perm kept, the batch is sorted on its own
+ *   (the layout's key kernel and stable radix sort) and each sorted array of the result is the
+ *   stable merge of the parent's with the batch's, parent readings first on equal keys: bit for
+ *   bit what qsc_obs_readings_layout gives for the parent's readings (in qsc_export_readings'
+ *   order) followed by the batch, under the same perm.  ins[i] = the number of parent readings
+ *   with a key <= batch reading i's (an upper bound inside one parent segment); batch reading i
+ *   goes to i + ins[i], parent reading e to e + #{i : ins[i] <= e} -- the parent's readings need
+ *   neither position nor key, a chunk of QSC_MERGE_CHUNK of them bounds its search range once and
+ *   stages it in LDS, and a chunk the batch does not touch is a shifted copy.  Widths, offsets, bin
+ *   order and *desc come from the new counts by qsc_obs_readings_layout's own stages.  Integer
+ *   arithmetic only; integer atomics for counts and max_repeat; the output bytes are a function of
+ *   the inputs.
+ * Sequence: qsc_obs_readings_count on the batch (*bad) -> cnt = the parent's cnt + the batch's ->
+ * qsc_obs_readings_merge -> qsc_obs_readings_fill -> (qsc_obs_schedule).
+ * ------------------------------------------------------------------------------------- */
+#define QSC_MERGE_CHUNK 1024 /* parent readings per workgroup of the merge */
+/* cnt[e] = the number of readings of cell (k[e], p[e]) the parent holds, e = 0 .. m - 1 (0 for k or
+ * p out of range).  Dense parent (codes != NULL; packed, iperm unused): codes[k][p] != 0xFF.  List
+ * parent (codes NULL): in the S-format segment of position iperm[p] (iperm[P]: the inverse of
+ * perm, -1 = no position), the upper minus the lower bound of k.  One thread per query; integer
+ * only, no atomics, no allocation, asynchronous, capturable. */
+QSC_API int qsc_obs_cell_counts(const uint8_t* codes, const void* packed, size_t packed_bytes,
+                                int64_t n, const qsc_obs_desc* d, const int32_t* iperm,
+                                const int32_t* k, const int32_t* p, int64_t m, int32_t* cnt,
+                                void* stream);
+/* bytes of packed_out (n + m readings) and of the merge's workspace (32 m for the batch's sort,
+ * 8 m for its sorted values and ins, the radix sort's buffers, and the count tables: it follows m,
+ * not n); 0 for arguments out of range (n + m >= 2^31 among them) */
+QSC_API size_t qsc_obs_readings_merge_packed_bytes(int64_t n, int64_t m, int32_t K, int32_t P,
+                                                   int32_t PT);
+QSC_API size_t qsc_obs_readings_merge_workspace_bytes(int64_t n, int64_t m, int32_t K, int32_t P,
+                                                      int32_t PT);
+/* SYNCHRONOUS (as qsc_obs_readings_layout: reads the totals).  packed / n / d / perm: the parent
+ * (d->nnz = n, left untouched); k, p, code (code_bytes 1 or 4): the batch, m >= 1 readings in any
+ * order, repeats allowed, checked by qsc_obs_readings_count; cnt[P]: the per-pixel counts of parent
+ * plus batch.  Outputs as qsc_obs_readings_layout's, for n + m readings.  *max_repeat (HOST
+ * pointer): on entry the parent's, on return the result's (only cells the batch touches can have
+ * grown).  QSC_EINVAL for n + m >= 2^31, a null pointer, a layout mismatch or buffers too small. */
+QSC_API int qsc_obs_readings_merge(const void* packed, size_t packed_bytes, int64_t n,
+                                   const qsc_obs_desc* d, const int32_t* perm, const int32_t* k,
+                                   const int32_t* p, const void* code, int32_t code_bytes,
+                                   int64_t m, const int32_t* cnt, int32_t* s_width, int64_t* s_off,
+                                   int32_t* c_width, int64_t* c_off, int32_t* c_kmap,
+                                   void* packed_out, size_t packed_out_bytes, void* ws,
+                                   size_t ws_bytes, qsc_obs_desc* desc, int32_t* max_repeat,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ PASS_SOURCES = ["qsc_pass_s.hip", "qsc_pass_c.hip", "qsc_pass_fused.hip", "qsc_p
 SOURCES = PASS_SOURCES + ["qsc_ops.hip", "qsc_obs.hip", "qsc_obs_readings.hip", "qsc_gram.hip", "qsc_spa.hip",
                           "qsc_map.hip", "qsc_smooth.hip", "qsc_info.hip", "qsc_sfit.hip", "qsc_cfit.hip",
                           "qsc_sfit_smooth.hip", "qsc_qfit.hip", "qsc_design.hip", "qsc_check.hip",
-                          "qsc_draw.hip", "qsc_obs_select.hip"]
+                          "qsc_draw.hip", "qsc_obs_select.hip", "qsc_obs_append.hip"]
 ARCH = os.environ.get("QSC_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: hipcc contracts a*b+c into FMA by default, which would change the
 # reference's separately rounded products and sums (get_tensor, quantize); FMAs that are

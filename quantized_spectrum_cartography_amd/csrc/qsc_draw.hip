@@ -37,6 +37,10 @@
 // cell is the same reading in both and gets the same code.  S is read in position order [Pp][RP],
 // the order of both arrays' keys.
 //
+// Listed cells (draw_list_kernel, qsc_draw_list).  A draw at cells given as lists (k, p, occurrence),
+// observed or not: one thread per query, the dense kernel's map value (natural planes) and the same
+// draw_code, with no present code to keep -- where nothing is drawn the output is 0xFF.
+//
 // No floating-point atomics, no workspace, no allocation; *invalid is an integer atomic.
 #include <hip/hip_runtime.h>
 
@@ -250,6 +254,27 @@ __global__ void __launch_bounds__(kBlock) draw_rd_c_kernel(
   }
 }
 
+// ---- listed cells: one thread per query (k, p, occurrence) -> a code, 0xFF where none is drawn ----
+template <bool LOGIT, bool LOG>
+__global__ void __launch_bounds__(kBlock) draw_list_kernel(
+    const int* __restrict__ k, const int* __restrict__ p, const int* __restrict__ occ, int64_t m,
+    int K, int P, const float* __restrict__ S, const float* __restrict__ C, int R, Link lk,
+    Edges E_, DrawKey key, uint8_t* __restrict__ code, int* __restrict__ invalid) {
+  QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= m) return;
+  const int kk = k[e], pp = p[e];
+  int ninv = 0, c = QSC_UNOBSERVED;
+  if (kk >= 0 && kk < K && pp >= 0 && pp < P) {
+    float t = 0.0f;  // (the dense kernel's sum: S natural planes, r ascending, by fma)
+    for (int r = 0; r < R; ++r) t = __builtin_fmaf(S[(int64_t)r * P + pp], C[(int64_t)r * K + kk], t);
+    c = draw_code<LOGIT, LOG>(t, QSC_UNOBSERVED, se, lk, (uint32_t)kk, (uint32_t)pp,
+                              occ ? (uint32_t)occ[e] : 0u, key, ninv);
+  }
+  code[e] = (uint8_t)c;
+  if (ninv) atomicAdd(invalid, ninv);
+}
+
 inline DrawKey make_key(int64_t seed, int32_t replicate) {
   DrawKey k;
   k.seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFu);
@@ -333,6 +358,30 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
   } while (0)
   QSC_INFO_DISPATCH(DRAW_RD_LAUNCH);
 #undef DRAW_RD_LAUNCH
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+QSC_API int qsc_draw_list(const int32_t* k, const int32_t* p, const int32_t* occ, int64_t n,
+                          int32_t K, int32_t P, const qsc_model* m, int32_t R, const float* S,
+                          const float* C, int64_t seed, int32_t replicate, uint8_t* code,
+                          int32_t* invalid, void* stream) {
+  if (!k || !p || !S || !C || !code || !invalid || !info_model_ok(m)) return QSC_EINVAL;
+  if (R < 1 || R > QSC_MAX_R || K < 1 || P < 1 || replicate < 0 || n < 1 ||
+      n >= ((int64_t)1 << 31) * kBlock)
+    return QSC_EINVAL;
+  const Link lk = make_link(m);
+  Edges E;
+  make_edges(m, &E);
+  const DrawKey key = make_key(seed, replicate);
+  const dim3 grid((unsigned)ceil_div(n, kBlock)), blk(kBlock);
+  hipStream_t hs = STREAM(stream);
+  const int kind = INFO_EXPECTED;
+#define DRAW_LIST_LAUNCH(LGT, LOGV, KD)                                                       \
+  hipLaunchKernelGGL((draw_list_kernel<LGT, LOGV>), grid, blk, 0, hs, k, p, occ, n, K, P, S, \
+                     C, R, lk, E, key, code, invalid)
+  QSC_INFO_DISPATCH(DRAW_LIST_LAUNCH);
+#undef DRAW_LIST_LAUNCH
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }

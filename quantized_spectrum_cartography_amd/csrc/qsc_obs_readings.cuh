@@ -1,7 +1,8 @@
 // qsc_obs_readings.cuh — the caller-kept sorted readings (`packed`) of the list packing: their
 // shapes, their carving and the search of a segment table.  Shared by qsc_obs_readings.hip (which
-// writes them and fills the entry formats from them), qsc_draw.hip (which redraws their codes) and
-// qsc_obs_select.hip (which exports the kept ones as lists).
+// writes them and fills the entry formats from them), qsc_draw.hip (which redraws their codes),
+// qsc_obs_select.hip (which exports the kept ones as lists) and qsc_obs_append.hip (which merges a
+// sorted batch into them, between the layout's own stages: declared at the end of this file).
 //
 // A sorted reading is  idx | code << 24  (idx = k or qlocal < 2^24, the wide format's own bound).
 #pragma once
@@ -69,3 +70,53 @@ inline size_t packed_carve(char* b, int64_t n, const Dims& d, Packed* pk) {
 inline bool n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
 
 }  // namespace
+
+// The stages of the list layout (qsc_obs_readings.hip defines them), in the order
+// qsc_obs_readings_layout runs them; qsc_obs_append.hip runs the same ones around its merges, so
+// that widths, offsets, bin order and the descriptor of an appended packing come from the very
+// code that lays out a re-sorted one.  Host functions; every stage is stream-ordered except
+// rd_layout_finish, which reads the totals back.
+namespace qsc {
+
+// the layout's workspace for a list of n readings
+struct RdWs {
+  int* iperm;        // [P]
+  int* poscnt;       // [Pp + 1]
+  int* ccount;       // [nt * Kp + 1]
+  int64_t* s_sizes;  // [ns + 1]
+  int64_t* c_sizes;  // [nc + 1]
+  int64_t* totals;   // [4]: s_off, c_off totals; then two ints, nnz and max_repeat
+  uint64_t* s_key;   // [n] x 3: S keys, C keys, sorted keys
+  uint64_t* c_key;
+  uint64_t* key_out;
+  uint32_t* s_val;   // [n] x 2
+  uint32_t* c_val;
+  void* cub;
+  size_t cub_bytes;
+};
+// carves b (may be null: sizing only) -> bytes, 0 for shapes out of range
+size_t rd_ws_carve(char* b, int64_t n, int32_t K, int32_t P, int32_t PT, RdWs* ws);
+// the kernels' LDS tables fit the device and K, PT fit a sorted reading's 24-bit index
+bool rd_layout_fits(int32_t K, int32_t P, int32_t PT);
+// inverse pixel order and per-position counts from cnt[P] -> w.iperm, w.poscnt; S-format slice
+// widths, offsets and list segments -> s_width, s_off, s_seg[Pp + 1]
+int rd_layout_positions(const RdWs& w, int32_t K, int32_t P, int32_t PT, const int32_t* perm,
+                        const int32_t* cnt, int32_t* s_width, int64_t* s_off, int* s_seg,
+                        hipStream_t s);
+// sort keys and values of both orders -> w.s_key, w.s_val, w.c_key, w.c_val; w.ccount[bin] += 1
+// per placed reading (the caller initialises w.ccount)
+int rd_layout_keys(const RdWs& w, const int32_t* k, const int32_t* p, const void* code,
+                   int32_t code_bytes, int64_t n, int32_t K, int32_t P, int32_t PT, int32_t nbins,
+                   hipStream_t s);
+// the stable radix sort of n (key, value) pairs with keys <= max_key
+int rd_sort_pairs(const RdWs& w, const uint64_t* key_in, uint64_t* key_out, const uint32_t* val_in,
+                  uint32_t* val_out, int64_t n, uint64_t max_key, hipStream_t s);
+// after the sorts: bin order, C-format widths, offsets and list segments from w.ccount -> c_width,
+// c_off, c_kmap, c_seg, c_kinv; the totals (SYNCHRONOUS) -> *desc, *max_repeat (the int the
+// caller's kernels left at ((int*)(w.totals + 2))[1])
+int rd_layout_finish(const RdWs& w, int32_t K, int32_t P, int32_t PT, int32_t nbins,
+                     const int* s_seg, const int64_t* s_off, int32_t* c_width, int64_t* c_off,
+                     int32_t* c_kmap, int* c_seg, int* c_kinv, qsc_obs_desc* desc,
+                     int32_t* max_repeat, hipStream_t s);
+
+}  // namespace qsc

@@ -276,22 +276,7 @@ size_t cub_scan64_bytes(int64_t n) {
   return b;
 }
 
-struct Ws {
-  int* iperm;       // [P]
-  int* poscnt;      // [Pp + 1]
-  int* ccount;      // [nt * Kp + 1]
-  int64_t* s_sizes; // [ns + 1]
-  int64_t* c_sizes; // [nc + 1]
-  int64_t* totals;  // [4]: s_off, c_off totals; then two ints, nnz and max_repeat
-  uint64_t* s_key;  // [n] x 3: S keys, C keys, sorted keys
-  uint64_t* c_key;
-  uint64_t* key_out;
-  uint32_t* s_val;  // [n] x 2
-  uint32_t* c_val;
-  void* cub;
-  size_t cub_bytes;
-};
-size_t ws_carve(char* b, int64_t n, int32_t P, const Dims& d, Ws* ws) {
+size_t ws_carve(char* b, int64_t n, int32_t P, const Dims& d, RdWs* ws) {
   char* w = b;
   ws->iperm = (int*)w;
   w += align_up((size_t)P * 4);
@@ -328,6 +313,121 @@ size_t ws_carve(char* b, int64_t n, int32_t P, const Dims& d, Ws* ws) {
 
 }  // namespace
 
+// ---- the stages of the layout (qsc_obs_readings.cuh declares them; qsc_obs_append.hip runs them
+// around its merges) ----
+namespace qsc {
+
+size_t rd_ws_carve(char* b, int64_t n, int32_t K, int32_t P, int32_t PT, RdWs* ws) {
+  Dims d;
+  if (!n_ok(n) || !dims_of(K, P, PT, &d)) return 0;
+  return ws_carve(b, n, P, d, ws);
+}
+
+bool rd_layout_fits(int32_t K, int32_t P, int32_t PT) {
+  Dims d;
+  if (!dims_of(K, P, PT, &d)) return false;
+  // rd_c_order_kernel's LDS (counts + order, 2 ints per bin) and rd_c_fill_kernel's (Kp + 1
+  // segment bounds) against the device's own limit: qsc_obs_layout's rule
+  int dev = 0, lds_max = 64 * 1024;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
+        v > 0)
+      lds_max = v;
+  }
+  if (d.Kp * 2 * (int64_t)sizeof(int) > lds_max) return false;
+  // a sorted reading keeps its index in 24 bits (the wide entry's own field)
+  return (int64_t)K < (1 << kIdxBits) && (int64_t)PT < (1 << kIdxBits);
+}
+
+int rd_layout_positions(const RdWs& w, int32_t K, int32_t P, int32_t PT, const int32_t* perm,
+                        const int32_t* cnt, int32_t* s_width, int64_t* s_off, int* s_seg,
+                        hipStream_t s) {
+  Dims d;
+  if (!dims_of(K, P, PT, &d)) return QSC_EINVAL;
+  const int Pp = (int)d.Pp, ns = (int)d.ns;
+  hipLaunchKernelGGL(rd_fill_int_kernel, dim3((unsigned)ceil_div(P, kBlock)), dim3(kBlock), 0, s,
+                     w.iperm, (int64_t)P, -1);
+  QSC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rd_positions_kernel, dim3((unsigned)ceil_div(Pp + 1, kBlock)), dim3(kBlock),
+                     0, s, perm, cnt, P, Pp, w.iperm, w.poscnt);
+  QSC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rd_s_width_kernel, dim3((unsigned)ceil_div(ns + 1, kBlock)), dim3(kBlock), 0,
+                     s, w.poscnt, ns, s_width, w.s_sizes);
+  QSC_CHECK_LAUNCH();
+  size_t cb = w.cub_bytes;
+  QSC_TRY(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.poscnt, s_seg, Pp + 1, s));
+  cb = w.cub_bytes;
+  QSC_TRY(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.s_sizes, s_off, ns + 1, s));
+  return QSC_OK;
+}
+
+int rd_layout_keys(const RdWs& w, const int32_t* k, const int32_t* p, const void* code,
+                   int32_t code_bytes, int64_t n, int32_t K, int32_t P, int32_t PT, int32_t nbins,
+                   hipStream_t s) {
+  Dims d;
+  if (!dims_of(K, P, PT, &d)) return QSC_EINVAL;
+  hipLaunchKernelGGL(rd_keys_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, s, k, p,
+                     code, code_bytes, n, K, P, (int)d.Pp, PT, (int)d.nt, (int)d.Kp, nbins, w.iperm,
+                     w.s_key, w.s_val, w.c_key, w.c_val, w.ccount);
+  QSC_CHECK_LAUNCH();
+  return QSC_OK;
+}
+
+int rd_sort_pairs(const RdWs& w, const uint64_t* key_in, uint64_t* key_out, const uint32_t* val_in,
+                  uint32_t* val_out, int64_t n, uint64_t max_key, hipStream_t s) {
+  size_t cb = w.cub_bytes;
+  QSC_TRY(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, key_in, key_out, val_in, val_out, (int)n,
+                                             0, key_bits(max_key), s));
+  return QSC_OK;
+}
+
+int rd_layout_finish(const RdWs& w, int32_t K, int32_t P, int32_t PT, int32_t nbins,
+                     const int* s_seg, const int64_t* s_off, int32_t* c_width, int64_t* c_off,
+                     int32_t* c_kmap, int* c_seg, int* c_kinv, qsc_obs_desc* desc,
+                     int32_t* max_repeat, hipStream_t s) {
+  Dims d;
+  if (!dims_of(K, P, PT, &d)) return QSC_EINVAL;
+  const int Pp = (int)d.Pp, ns = (int)d.ns, nt = (int)d.nt, nks = (int)d.nks, Kp = (int)d.Kp;
+  const int nc = (int)d.nc, nb = (int)d.nb;
+  const int wide = (K > 4096 || PT > 4096 || nbins > 15) ? 1 : 0;
+  // C-format: bin order and widths per tile, list segments
+  hipLaunchKernelGGL(rd_c_order_kernel, dim3((unsigned)nt), dim3(kBlock), Kp * 2 * sizeof(int), s,
+                     w.ccount, K, nks, c_width, w.c_sizes, c_kmap, c_kinv);
+  QSC_CHECK_LAUNCH();
+  size_t cb = w.cub_bytes;
+  QSC_TRY(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.ccount, c_seg, nb + 1, s));
+  cb = w.cub_bytes;
+  QSC_TRY(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.c_sizes, c_off, nc + 1, s));
+
+  int* scal = (int*)(w.totals + 2);  // [0] nnz, [1] max_repeat
+  QSC_TRY(hipMemcpyAsync(w.totals, s_off + ns, 8, hipMemcpyDeviceToDevice, s));
+  QSC_TRY(hipMemcpyAsync(w.totals + 1, c_off + nc, 8, hipMemcpyDeviceToDevice, s));
+  QSC_TRY(hipMemcpyAsync(scal, s_seg + Pp, sizeof(int), hipMemcpyDeviceToDevice, s));
+  int64_t host_tot[3];
+  QSC_TRY(hipMemcpyAsync(host_tot, w.totals, sizeof(host_tot), hipMemcpyDeviceToHost, s));
+  QSC_TRY(hipStreamSynchronize(s));
+  const int32_t nnz = (int32_t)(host_tot[2] & 0xFFFFFFFF);
+  const int32_t rep = (int32_t)(host_tot[2] >> 32);
+  desc->K = K;
+  desc->P = P;
+  desc->Pp = Pp;
+  desc->PT = PT;
+  desc->ntiles = nt;
+  desc->nks = nks;
+  desc->wide = wide;
+  desc->nbins = nbins;
+  desc->s_entries = host_tot[0] + QSC_ENTRY_TAIL;
+  desc->c_entries = host_tot[1] + QSC_ENTRY_TAIL;
+  desc->nnz = nnz;
+  desc->rowfmt = 0;
+  desc->reserved_ = 0;
+  if (max_repeat) *max_repeat = rep;
+  return QSC_OK;
+}
+
+}  // namespace qsc
+
 extern "C" {
 
 QSC_API int qsc_obs_readings_count(const int32_t* k, const int32_t* p, const void* code,
@@ -353,7 +453,7 @@ QSC_API size_t qsc_obs_readings_packed_bytes(int64_t n, int32_t K, int32_t P, in
 
 QSC_API size_t qsc_obs_readings_workspace_bytes(int64_t n, int32_t K, int32_t P, int32_t PT) {
   Dims d;
-  Ws ws;
+  RdWs ws;
   if (!n_ok(n) || !dims_of(K, P, PT, &d)) return 0;
   return ws_carve(nullptr, n, P, d, &ws);
 }
@@ -371,100 +471,36 @@ QSC_API int qsc_obs_readings_layout(const int32_t* k, const int32_t* p, const vo
       (code_bytes != 1 && code_bytes != 4) || !dims_of(K, P, PT, &d))
     return QSC_EINVAL;
   Packed pk;
-  Ws w;
+  RdWs w;
   if (packed_bytes < packed_carve((char*)packed, n, d, &pk) ||
       ws_bytes < ws_carve((char*)ws, n, P, d, &w))
     return QSC_EINVAL;
-  // rd_c_order_kernel's LDS (counts + order, 2 ints per bin) and rd_c_fill_kernel's (Kp + 1
-  // segment bounds) against the device's own limit: qsc_obs_layout's rule
-  int dev = 0, lds_max = 64 * 1024;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
-        v > 0)
-      lds_max = v;
-  }
-  if (d.Kp * 2 * (int64_t)sizeof(int) > lds_max) return QSC_EINVAL;
-  const int wide = (K > 4096 || PT > 4096 || nbins > 15) ? 1 : 0;
-  // a sorted reading keeps its index in 24 bits (the wide entry's own field)
-  if ((int64_t)K >= (1 << kIdxBits) || (int64_t)PT >= (1 << kIdxBits)) return QSC_EINVAL;
-  const int Pp = (int)d.Pp, ns = (int)d.ns, nt = (int)d.nt, nks = (int)d.nks, Kp = (int)d.Kp;
-  const int nc = (int)d.nc, nb = (int)d.nb;
+  if (!rd_layout_fits(K, P, PT)) return QSC_EINVAL;
+  const int Pp = (int)d.Pp;
   hipStream_t s = STREAM(stream);
-  hipError_t e;
 
   // positions: inverse pixel order, per-position counts, slice widths, list segments
-  hipLaunchKernelGGL(rd_fill_int_kernel, dim3((unsigned)ceil_div(P, kBlock)), dim3(kBlock), 0, s,
-                     w.iperm, (int64_t)P, -1);
-  QSC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rd_positions_kernel, dim3((unsigned)ceil_div(Pp + 1, kBlock)), dim3(kBlock),
-                     0, s, perm, cnt, P, Pp, w.iperm, w.poscnt);
-  QSC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rd_s_width_kernel, dim3((unsigned)ceil_div(ns + 1, kBlock)), dim3(kBlock), 0,
-                     s, w.poscnt, ns, s_width, w.s_sizes);
-  QSC_CHECK_LAUNCH();
-  size_t cb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.poscnt, pk.s_seg, Pp + 1, s);
-  QSC_TRY(e);
-  cb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.s_sizes, s_off, ns + 1, s);
-  QSC_TRY(e);
+  int rc = rd_layout_positions(w, K, P, PT, perm, cnt, s_width, s_off, pk.s_seg, s);
+  if (rc != QSC_OK) return rc;
 
   // keys of both orders and the (tile, bin) counts, then the two stable sorts
-  QSC_TRY(hipMemsetAsync(w.ccount, 0, (size_t)(nb + 1) * sizeof(int), s));
-  hipLaunchKernelGGL(rd_keys_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, s, k, p,
-                     code, code_bytes, n, K, P, Pp, PT, nt, Kp, nbins, w.iperm, w.s_key, w.s_val,
-                     w.c_key, w.c_val, w.ccount);
-  QSC_CHECK_LAUNCH();
-  cb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.s_key, w.key_out, w.s_val, pk.s_rd, (int)n,
-                                         0, key_bits((uint64_t)Pp * (uint64_t)K), s);
-  QSC_TRY(e);
+  QSC_TRY(hipMemsetAsync(w.ccount, 0, (size_t)(d.nb + 1) * sizeof(int), s));
+  rc = rd_layout_keys(w, k, p, code, code_bytes, n, K, P, PT, nbins, s);
+  if (rc != QSC_OK) return rc;
+  rc = rd_sort_pairs(w, w.s_key, w.key_out, w.s_val, pk.s_rd, n, (uint64_t)Pp * (uint64_t)K, s);
+  if (rc != QSC_OK) return rc;
   int* scal = (int*)(w.totals + 2);  // [0] nnz, [1] max_repeat
   QSC_TRY(hipMemsetAsync(scal, 0, 2 * sizeof(int64_t), s));
   hipLaunchKernelGGL(rd_max_repeat_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, s,
                      w.key_out, pk.s_seg + Pp, n, scal + 1);
   QSC_CHECK_LAUNCH();
-  cb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(
-      w.cub, cb, w.c_key, w.key_out, w.c_val, pk.c_rd, (int)n, 0,
-      key_bits((uint64_t)nt * (uint64_t)Kp * (uint64_t)PT), s);
-  QSC_TRY(e);
+  rc = rd_sort_pairs(w, w.c_key, w.key_out, w.c_val, pk.c_rd, n,
+                     (uint64_t)d.nt * (uint64_t)d.Kp * (uint64_t)PT, s);
+  if (rc != QSC_OK) return rc;
 
-  // C-format: bin order and widths per tile, list segments
-  hipLaunchKernelGGL(rd_c_order_kernel, dim3((unsigned)nt), dim3(kBlock), Kp * 2 * sizeof(int), s,
-                     w.ccount, K, nks, c_width, w.c_sizes, c_kmap, pk.c_kinv);
-  QSC_CHECK_LAUNCH();
-  cb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.ccount, pk.c_seg, nb + 1, s);
-  QSC_TRY(e);
-  cb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.c_sizes, c_off, nc + 1, s);
-  QSC_TRY(e);
-
-  QSC_TRY(hipMemcpyAsync(w.totals, s_off + ns, 8, hipMemcpyDeviceToDevice, s));
-  QSC_TRY(hipMemcpyAsync(w.totals + 1, c_off + nc, 8, hipMemcpyDeviceToDevice, s));
-  QSC_TRY(hipMemcpyAsync(scal, pk.s_seg + Pp, sizeof(int), hipMemcpyDeviceToDevice, s));
-  int64_t host_tot[3];
-  QSC_TRY(hipMemcpyAsync(host_tot, w.totals, sizeof(host_tot), hipMemcpyDeviceToHost, s));
-  QSC_TRY(hipStreamSynchronize(s));
-  const int32_t nnz = (int32_t)(host_tot[2] & 0xFFFFFFFF);
-  const int32_t rep = (int32_t)(host_tot[2] >> 32);
-  desc->K = K;
-  desc->P = P;
-  desc->Pp = Pp;
-  desc->PT = PT;
-  desc->ntiles = nt;
-  desc->nks = nks;
-  desc->wide = wide;
-  desc->nbins = nbins;
-  desc->s_entries = host_tot[0] + QSC_ENTRY_TAIL;
-  desc->c_entries = host_tot[1] + QSC_ENTRY_TAIL;
-  desc->nnz = nnz;
-  desc->rowfmt = 0;
-  desc->reserved_ = 0;
-  if (max_repeat) *max_repeat = rep;
-  return QSC_OK;
+  // C-format bin order, widths, offsets and list segments; the totals; the descriptor
+  return rd_layout_finish(w, K, P, PT, nbins, pk.s_seg, s_off, c_width, c_off, c_kmap, pk.c_seg,
+                          pk.c_kinv, desc, max_repeat, s);
 }
 
 QSC_API int qsc_obs_readings_fill(const void* packed, size_t packed_bytes, int64_t n,

@@ -1,6 +1,7 @@
 """The post-solve estimators (not in the reference): confidence, design, check_fit, the Newton
 fits fit_S, fit_C, fit_S_smooth and fit_noise, model_nll, calibrate, bootstrap, cross_validate,
-and the stage of solve() that runs them on its
+acquire (the sequential-sensing loop over design, Observations.append and the fits), and the
+stage of solve() that runs them on its
 result (check_post_solve, post_solve).  Every public function validates its arguments before
 anything touches a device; the `_*_pos` drivers take a position-order S (Pp, RP) and device
 tensors.  qmc re-exports the names: qmc.fit_S etc. stay the user-facing spellings.
@@ -854,6 +855,101 @@ def calibrate(obs, S, C, rounds=2, ridge_s=0.0, ridge_c=0.0, fit=("scale", "shif
         out.fits.append(q)
     out.S, out.C, out.obs, out.noise_std = S, C, obs, obs.noise_std
     return out
+
+
+@dataclass
+class AcquireRound:
+    sites: torch.Tensor     # (sites, 2) int64 rows (i, j), CPU: the pixels chosen, best first
+    gain: torch.Tensor      # (sites,) fp32, CPU: their predicted gains (+inf: a first look)
+    added: int              # readings appended in the round
+
+
+@dataclass
+class AcquireResult:
+    obs: Observations       # the observations after the last round
+    S: torch.Tensor         # the loss fields after the last refit (the input where refit=())
+    C: torch.Tensor         # the spectra likewise
+    rounds: List[AcquireRound]
+
+
+ACQUIRE_REFIT = ("S", "C")
+
+
+def check_acquire(loss, measure, rounds, sites, weights, K, criterion="D", kind="expected",
+                  ridge=0.0, refit=("S",), generator=None, P=None):
+    """Validate acquire's arguments (before anything touches a device): a likelihood and a free S
+    (no generator), a callable `measure`, rounds >= 1, 1 <= sites (<= P where given), check_design's
+    rules with whole numbers of readings as weights, refit a subset of ("S", "C").
+    -> (the plan as an int64 CPU tensor (K,), refit as a tuple).  Raises ValueError."""
+    if generator is not None:
+        raise ValueError("acquire applies to free S only: with a generator S is not a free "
+                         "parameter")
+    w = check_design(criterion, kind, ridge, loss, weights, K)
+    if not callable(measure):
+        raise ValueError("measure must be a callable: (k, i, j, obs) -> codes")
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or rounds < 1:
+        raise ValueError("rounds must be an int >= 1, got %r" % (rounds,))
+    if isinstance(sites, bool) or not isinstance(sites, int) or sites < 1 or \
+            (P is not None and sites > int(P)):
+        raise ValueError("sites must be an int in [1, number of pixels], got %r" % (sites,))
+    refit = (refit,) if isinstance(refit, str) else tuple(refit)
+    if any(b not in ACQUIRE_REFIT for b in refit):
+        raise ValueError("refit may name %s, got %r" % (list(ACQUIRE_REFIT), refit))
+    if w is None:
+        w = torch.ones(int(K), dtype=torch.float32)
+    if not bool((w == w.round()).all()) or float(w.sum()) < 1.0:
+        raise ValueError("acquire plans whole readings: the weights must be whole numbers with "
+                         "at least one reading")
+    return w.to(torch.int64), refit
+
+
+def acquire(obs, S, C, measure, rounds, sites, weights=None, criterion="D", kind="expected",
+            ridge=0.0, refit=("S",), ridge_s=0.0, ridge_c=0.0, max_steps=30, generator=None):
+    """Sequential sensing: design -> measure -> append -> refit, `rounds` times.
+
+    Each round runs design(obs, S, C, weights, criterion, kind, ridge), takes result.best(sites)
+    (first looks, gain +inf, come first), plans weights[k] readings of bin k at each chosen pixel
+    (default: one of every bin), asks code = measure(k, i, j, obs) for them (int64 lists on obs.device,
+    site by site in the order chosen, bins ascending; -> an integer tensor of codes), appends them
+    (obs.append: a list parent is merged, not re-sorted) and refits: fit_S(obs, C, S_init=S,
+    ridge=ridge_s) where "S" is in refit, then fit_C(obs, S, C_init=C, ridge=ridge_c) where "C" is.
+    refit=() leaves S and C as given.  acquire.simulate(S_true, C_true, seed) is a `measure` that
+    draws the readings from a truth (obs.draw: the data do not depend on how the acquisition is
+    cut into rounds).  The input obs is left untouched.
+    -> AcquireResult(obs, S, C, rounds: per round the sites, their predicted gains and the number
+    of readings added).  Raises ValueError for loss="squared", a generator, or arguments out of
+    range, before any device call."""
+    w, refit = check_acquire(getattr(obs, "loss", None), measure, rounds, sites, weights,
+                             getattr(obs, "K", C.shape[-1]), criterion, kind, ridge, refit,
+                             generator, getattr(obs, "P", None))
+    plan = torch.repeat_interleave(torch.arange(w.numel()), w)  # one site's bins, ascending
+    wf = w.to(torch.float32)
+    log = []
+    for _ in range(rounds):
+        d = design(obs, S, C, weights=wf, criterion=criterion, kind=kind, ridge=ridge)
+        ij = d.best(sites).to(obs.device)
+        gain = d.gain.reshape(-1)[ij[:, 0] * obs.J + ij[:, 1]]
+        k = plan.to(obs.device).repeat(sites)
+        i = ij[:, 0].repeat_interleave(plan.numel())
+        j = ij[:, 1].repeat_interleave(plan.numel())
+        obs = obs.append(k, i, j, measure(k, i, j, obs))
+        if "S" in refit:
+            S = fit_S(obs, C, S_init=S, ridge=ridge_s, max_steps=max_steps).S
+        if "C" in refit:
+            C = fit_C(obs, S, C_init=C, ridge=ridge_c, max_steps=max_steps).C
+        log.append(AcquireRound(sites=ij.cpu(), gain=gain.cpu(), added=int(k.numel())))
+    return AcquireResult(obs=obs, S=S, C=C, rounds=log)
+
+
+def _simulate(S_true, C_true, seed=0, replicate=0):
+    """A `measure` for acquire that draws every planned reading from the model of the
+    observations at the truth (S_true, C_true): obs.draw with the given seed and replicate."""
+    def measure(k, i, j, obs):
+        return obs.draw(k, i, j, S_true, C_true, seed=seed, replicate=replicate)
+    return measure
+
+
+acquire.simulate = _simulate
 
 
 @dataclass

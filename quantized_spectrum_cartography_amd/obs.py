@@ -271,35 +271,45 @@ class Observations:
         self = cls.__new__(cls)
         PT, nbins = self._setup(K, I, J, bin_boundaries, noise_std, offset, log_model, tile,
                                 R_hint, loss, schedule)
-        P = self.P
+        kd, pd, cd = self._device_readings(k, i, j, code, I, J)
+        self.device = kd.device
+        self._pack_readings(kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint)
+        return self
+
+    @staticmethod
+    def _device_readings(k, i, j, code, I, J):
+        """Checked host or device lists -> the device lists the packing kernels take: int32 k,
+        int32 p = i J + j, uint8 or int32 code (None: no codes)."""
         # (values past int32 stay out of range instead of wrapping into it)
         kd = _dev(k).to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
-        dev = kd.device
-        self.device = dev
         # p = i J + j in int64 with out-of-grid (i, j) mapped to -1 (counted by the device)
         i64, j64 = _dev(i).to(torch.int64), _dev(j).to(torch.int64)
         inside = (i64 >= 0) & (i64 < I) & (j64 >= 0) & (j64 < J)
         pd = torch.where(inside, i64 * J + j64, torch.full_like(i64, -1)).to(torch.int32)
+        if code is None:
+            return kd, pd, None
         cd = _dev(code)
         cd = (cd if cd.dtype == torch.uint8 else
               cd.to(torch.int64).clamp(-1, 1 << 20).to(torch.int32)).contiguous()
-        self._pack_readings(kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint)
-        return self
+        return kd, pd, cd
 
-    def _pack_readings(self, kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint):
+    def _pack_readings(self, kd, pd, cd, n, perm, count_hook, PT, nbins, R_hint, cnt=None):
         """from_readings from the device lists on (after _setup): int32 k, int32 p = i J + j,
-        uint8 or int32 code, n of each: count, order, layout (two sorts), fill."""
+        uint8 or int32 code, n of each: count, order, layout (two sorts), fill.  cnt: the
+        per-pixel counts of a list the caller has counted and found in range already (append)."""
         K, I, J, P, dev = self.K, self.I, self.J, self.P, self.device
         cb = 1 if cd.dtype == torch.uint8 else 4
         s = _lib.stream()
-        cnt = torch.empty(P, dtype=torch.int32, device=dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.call("qsc_obs_readings_count", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, n, K, P,
-                  nbins, _lib.ptr(cnt), _lib.ptr(bad), s)
-        nbad = int(bad.item())
-        if nbad:
-            raise ValueError("%d of %d readings have k outside [0, %d), (i, j) outside the "
-                             "%d x %d grid or a code outside [0, %d)" % (nbad, n, K, I, J, nbins))
+        if cnt is None:
+            cnt = torch.empty(P, dtype=torch.int32, device=dev)
+            bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.call("qsc_obs_readings_count", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, n, K,
+                      P, nbins, _lib.ptr(cnt), _lib.ptr(bad), s)
+            nbad = int(bad.item())
+            if nbad:
+                raise ValueError("%d of %d readings have k outside [0, %d), (i, j) outside the "
+                                 "%d x %d grid or a code outside [0, %d)"
+                                 % (nbad, n, K, I, J, nbins))
         self.codes = None
         self.counts = cnt
         perm = self._order(cnt, perm, count_hook)
@@ -616,6 +626,124 @@ class Observations:
         i = torch.div(p, self.J, rounding_mode="floor")
         return k, i, p - i * self.J, c
 
+    # ---- growth: occurrences, draw, append (include/qsc.h, "Growing a list packing") ----------
+    def _cells(self, k, i, j):
+        """Checked device lists (int32 k, int32 p, their number) of cells given as (k, i, j).
+        Raises ValueError with the number of cells outside the map."""
+        # (check_readings' rules for three lists: k stands in for the codes)
+        K, I, J, m = self.check_readings(k, i, j, k, (self.K, self.I, self.J))
+        kd, pd, _ = self._device_readings(k, i, j, None, I, J)
+        nbad = int(((kd < 0) | (kd >= K) | (pd < 0)).sum())
+        if nbad:
+            raise ValueError("%d of %d cells have k outside [0, %d) or (i, j) outside the %d x %d "
+                             "grid" % (nbad, m, K, I, J))
+        return kd, pd, m
+
+    def occurrences(self, k, i, j):
+        """(m,) int32 on the device: the occurrence number j_occ every reading of the list of
+        cells (k, i, j) (1-D integer tensors, repeats allowed) will have once appended -- the
+        number of readings of its cell this object holds (qsc_obs_cell_counts) plus its place
+        among the earlier readings of the same cell in the list.  Raises ValueError for lists of
+        unequal length or cells outside the map."""
+        kd, pd, m = self._cells(k, i, j)
+        cnt = torch.empty(m, dtype=torch.int32, device=self.device)
+        if self.codes is not None:
+            _lib.call("qsc_obs_cell_counts", _lib.ptr(self.codes), None, 0, 0, self.desc, None,
+                      _lib.ptr(kd), _lib.ptr(pd), m, _lib.ptr(cnt), _lib.stream())
+        else:
+            _lib.call("qsc_obs_cell_counts", None, _lib.ptr(self._packed), self._packed.numel(),
+                      self._n, self.desc, _lib.ptr(self.iperm()), _lib.ptr(kd), _lib.ptr(pd), m,
+                      _lib.ptr(cnt), _lib.stream())
+        # the place inside the list: a stable sort by cell (m is a batch: not the hot path)
+        cell, order = torch.sort(kd.to(torch.int64) * self.P + pd, stable=True)
+        idx = torch.arange(m, device=self.device)
+        first = torch.ones(m, dtype=torch.bool, device=self.device)
+        first[1:] = cell[1:] != cell[:-1]
+        start = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)), 0).values
+        rank = torch.empty(m, dtype=torch.int32, device=self.device)
+        rank[order] = (idx - start).to(torch.int32)
+        return cnt + rank
+
+    def draw(self, k, i, j, S, C, seed=0, replicate=0, allow_invalid=False):
+        """(m,) uint8 codes drawn from this object's model at (S, C) for new readings of the cells
+        (k, i, j), observed so far or not: draw_readings with occurrence=self.occurrences(k, i, j),
+        so that reading j_occ of a cell gets the same code however an acquisition is cut into
+        batches -- the code resample() would give it once it is appended."""
+        occ = self.occurrences(k, i, j)
+        return draw_readings(k, i, j, S, C, (self.K, self.I, self.J), self.bin_boundaries,
+                             self.noise_std, self.offset, self.log_model, self.loss, seed,
+                             replicate, occurrence=occ, allow_invalid=allow_invalid)
+
+    def append(self, k, i, j, code, perm="keep"):
+        """A new Observations that holds this object's readings followed by the batch (k, i, j,
+        code) (from_readings' four lists: any order, repeats allowed), with this one's model, loss,
+        tile, R_hint and schedule flag.  The result is a list packing, bit for bit
+        from_readings(cat(self.readings(), batch), perm=...); this object is left untouched, so
+        hipGraphs captured on it stay valid.
+        A list parent with perm="keep" is not re-sorted: the batch alone is sorted and merged into
+        the kept sorted readings (qsc_obs_readings_merge), the tables are laid out from the new
+        counts, the row format is re-evaluated and the entries are filled and scheduled as
+        from_readings does.  perm="fresh" (the pixels ordered by the new counts) changes both sort
+        keys, and a dense parent keeps no sorted readings -- its first append is the one that
+        forms them: both export, concatenate and re-sort (perm="keep" keeps a dense parent's
+        pixel order too), and later appends to the result merge.
+        Raises ValueError for lists of unequal length or non-integer dtypes and an unknown perm
+        (before any device call), and with the number of readings out of range; nothing is
+        built then."""
+        K, I, J, m = self.check_readings(k, i, j, code, (self.K, self.I, self.J))
+        if perm not in ("keep", "fresh"):
+            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+        n, P = self.nnz, self.P
+        if n + m >= 2 ** 31:
+            raise ValueError("at most 2^31 - 1 readings are supported, got %d + %d" % (n, m))
+        kd, pd, cd = self._device_readings(k, i, j, code, I, J)
+        PT, nbins = int(self.desc.PT), int(self.desc.nbins)
+        cb = 1 if cd.dtype == torch.uint8 else 4
+        s = _lib.stream()
+        bcnt = torch.empty(P, dtype=torch.int32, device=self.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.call("qsc_obs_readings_count", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, m, K, P,
+                  nbins, _lib.ptr(bcnt), _lib.ptr(bad), s)
+        nbad = int(bad.item())
+        if nbad:
+            raise ValueError("%d of %d readings have k outside [0, %d), (i, j) outside the "
+                             "%d x %d grid or a code outside [0, %d)" % (nbad, m, K, I, J, nbins))
+        new = self._child()
+        if self.codes is not None or perm == "fresh":
+            pk, pp, pc, n0 = self._export(None, None, 0, 0, self.RANGE, 0)
+            new._pack_readings(torch.cat((pk[:n0], kd)), torch.cat((pp[:n0], pd)),
+                               torch.cat((pc[:n0], cd.to(torch.uint8))), n0 + m,
+                               self.perm if perm == "keep" else None, None, PT, nbins, new.R_hint,
+                               cnt=self.counts + bcnt)
+            return new
+        new.codes = None
+        new.counts = self.counts + bcnt
+        new.perm = self.perm
+        new._alloc_tables(PT)
+        L = _lib.lib()
+        nb = L.qsc_obs_readings_merge_packed_bytes(n, m, K, P, PT)
+        wb = L.qsc_obs_readings_merge_workspace_bytes(n, m, K, P, PT)
+        if nb == 0 or wb == 0:
+            raise ValueError("%d + %d readings of shape %r with tile %d are out of the merge's "
+                             "range" % (n, m, (K, I, J), PT))
+        new._packed = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        new._n = n + m
+        ws = torch.empty(wb, dtype=torch.uint8, device=self.device)  # (follows m; not cached)
+        desc = _lib.QscObsDesc()
+        rep = ctypes.c_int32(int(self.max_repeat))
+        _lib.call("qsc_obs_readings_merge", _lib.ptr(self._packed), self._packed.numel(), n,
+                  self.desc, _lib.ptr(self.perm), _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(cd), cb, m,
+                  _lib.ptr(new.counts), _lib.ptr(new.s_width), _lib.ptr(new.s_off),
+                  _lib.ptr(new.c_width), _lib.ptr(new.c_off), _lib.ptr(new.c_kmap),
+                  _lib.ptr(new._packed), nb, _lib.ptr(ws), wb, desc, ctypes.byref(rep), s)
+        del ws
+        if int(desc.nnz) != n + m:  # a parent's perm that gives some pixel of the batch no position
+            raise ValueError("perm places only %d of the %d readings: every pixel that has a "
+                             "reading needs a position" % (int(desc.nnz), n + m))
+        new.max_repeat = int(rep.value)
+        new._finish(desc, new.R_hint)
+        return new
+
     def signed_rows_ok(self, R):
         if os.environ.get("QSC_SIGNED_ROWS", "1") == "0":  # A/B switch (tuning runs)
             return False
@@ -711,3 +839,61 @@ class Observations:
         _lib.call("qsc_perm_scatter", _lib.ptr(Xp.contiguous()), _lib.ptr(self.perm), R, self.P,
                   self.Pp, _lib.ptr(out), _lib.stream())
         return out
+
+
+def check_draw_readings(k, i, j, S, C, shape, loss="probit", seed=0, replicate=0, occurrence=None):
+    """Host-side checks of draw_readings' arguments, before any device call: check_readings'
+    rules for the three lists of cells, check_resample's for loss, S, C, seed and replicate, and
+    `occurrence` a 1-D integer tensor of the lists' length or None.  -> (K, I, J, m, R, seed as
+    a signed 64-bit value).  Raises ValueError."""
+    K, I, J, m = Observations.check_readings(k, i, j, k, shape)
+    R, seed64 = Observations.check_resample(loss, K, I, J, S, C, seed, replicate)
+    if occurrence is not None:
+        Observations.check_readings(k, i, j, occurrence, shape)  # (one length, an integer dtype)
+    return K, I, J, m, R, seed64
+
+
+def draw_readings(k, i, j, S, C, shape, bin_boundaries, noise_std, offset=0.0, log_model=False,
+                  loss="probit", seed=0, replicate=0, occurrence=None, allow_invalid=False):
+    """(m,) uint8 codes on the device, drawn from the model at (S, C) at the listed cells: reading
+    e is bin k[e] at pixel (i[e], j[e]) of the shape = (K, I, J) map, observed so far or not
+    (qsc_draw_list, include/qsc.h).  The rule is Observations.resample's word for word, by the
+    same device functions: the Philox counter is (k, p, occurrence, replicate), so with
+    occurrence[e] the reading's number in its cell (None: all 0) the code is the one resample
+    gives that reading of a packed object.  Observations.draw fills `occurrence` in from what the
+    object holds.  A reading nothing can be drawn for (log model with T_hat + offset <= 0; a NaN
+    T_hat) gets 0xFF; unless allow_invalid, their number raises ValueError.  S (R,1,I,J) or
+    (R,I,J) or (R,I J), C (R,K); the model arguments are Observations'.  Raises ValueError for
+    lists of unequal length, shapes that do not match, loss="squared" (not a likelihood) or
+    seed / replicate out of range before any device call, and for cells outside the map or a
+    negative occurrence."""
+    K, I, J, m, R, seed64 = check_draw_readings(k, i, j, S, C, shape, loss, seed, replicate,
+                                                occurrence)
+    model = _lib.make_model(bin_boundaries, noise_std, offset if log_model else 0.0, log_model,
+                            loss=loss)
+    kd, pd, _ = Observations._device_readings(k, i, j, None, I, J)
+    dev = kd.device
+    nbad = int(((kd < 0) | (kd >= K) | (pd < 0)).sum())
+    if nbad:
+        raise ValueError("%d of %d cells have k outside [0, %d) or (i, j) outside the %d x %d "
+                         "grid" % (nbad, m, K, I, J))
+    od = None
+    if occurrence is not None:
+        o64 = _dev(occurrence).to(torch.int64)
+        if int(((o64 < 0) | (o64 >= 2 ** 31)).sum()):
+            raise ValueError("occurrence numbers must be in [0, 2^31)")
+        od = o64.to(torch.int32).contiguous()
+    Cd = _dev(C.detach().to(torch.float32)).reshape(R, K).contiguous()
+    Sd = _dev(S.detach().to(torch.float32)).reshape(R, I * J).contiguous()
+    code = torch.empty(m, dtype=torch.uint8, device=dev)
+    invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("qsc_draw_list", _lib.ptr(kd), _lib.ptr(pd), _lib.ptr(od), m, K, I * J, model, R,
+              _lib.ptr(Sd), _lib.ptr(Cd), seed64, int(replicate), _lib.ptr(code),
+              _lib.ptr(invalid), _lib.stream())
+    if not allow_invalid:
+        left = int((code == _lib.UNOBSERVED).sum())
+        if left:
+            raise ValueError("%d of %d readings cannot be drawn (%d with T_hat + offset <= 0 "
+                             "under the log model); allow_invalid=True returns them as 0xFF"
+                             % (left, m, int(invalid.item())))
+    return code

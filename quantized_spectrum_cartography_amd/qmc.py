@@ -27,13 +27,14 @@ from .fits import (  # noqa: F401
     DESIGN_CRITERIA, INFO_KINDS, BootstrapResult, CalibrateResult, CheckResult, ConfidenceResult,
     CrossValidateResult, DesignResult, FitCResult, bootstrap, check_bootstrap,
     check_cross_validate, cross_validate,
+    AcquireResult, AcquireRound, acquire, check_acquire,
     FitNoiseResult, FitSResult, FitSSmoothResult, _fit_c_pos, _fit_noise_pos, _fit_s_pos,
     _fit_s_smooth_pos, _sfit_smooth_bufs, _sfit_smooth_visit, calibrate, check_confidence, check_design,
     check_fit, check_fit_noise, check_polish_c, check_post_solve, confidence, default_confidence_ridge,
     design, fit_C, fit_noise,
     fit_S, fit_S_smooth, model_nll, post_solve, shifted_boundaries)
 from .fused import PassEngine, check_smooth
-from .obs import Observations
+from .obs import Observations, check_draw_readings, draw_readings  # noqa: F401
 # the run driver and the hipGraph mechanics live in runs.py; these spellings stay importable
 from .runs import (  # noqa: F401
     GRAPH_MAX_ITERS, AlternatingSolver, abandon_capture, capture_stream, cost_history,
