@@ -620,6 +620,8 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+// the size of one array of a carved workspace: the next one starts 256-byte aligned
+inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // compute units of the current device (cached per device id)
 inline int cu_count() {

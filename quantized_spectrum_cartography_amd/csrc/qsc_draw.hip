@@ -17,25 +17,21 @@
 //
 // Dense (draw_codes_kernel).  codes[K][P] holds about one observed cell in ten.  A thread per cell
 // with an early exit would run the bin loop with about a tenth of its lanes; the kernel compacts
-// instead: a workgroup takes kTile consecutive cells of one bin k, every thread reads 16 of them
-// (one 16-byte load where P and the pointers allow it, byte loads otherwise), the observed ones'
-// offsets are appended to a list in LDS (an integer LDS counter: the order of the list varies,
-// the result of a cell does not depend on it), and the threads then share the list, full waves
-// until its tail.  The drawn codes are set into an LDS copy of the tile, which is written back in
-// the layout it was read in.  k is uniform in a workgroup: c_k and the edges sit in LDS and are
-// read at uniform addresses.  S is read as natural [R][P] planes: the cells of a tile are
+// instead: a workgroup takes kTile consecutive cells of one bin k as qsc_obs_tile.cuh's dense tile
+// (see there: the load, the ascending list of the observed cells' offsets by stage_observed -- the
+// ordered scan the exports use, no atomics decide a position: 112.6 us per call at C3 against 161.0
+// with an LDS-atomic append, profiles/obswalk/ -- and the write-back), and the threads share the
+// list, full waves until its tail.  k is uniform in a workgroup: c_k and the edges sit in LDS and
+// are read at uniform addresses.  S is read as natural [R][P] planes: the cells of a tile are
 // consecutive pixels, so a plane's reads fall into one 16 KiB window per workgroup; position rows
 // would need the inverse permutation and give scattered 16- to 64-byte reads.
 //
 // Readings (draw_rd_s_kernel, draw_rd_c_kernel).  Both sorted arrays of `packed` are redrawn, each
-// from its own keys: the S-format array by slice (one wave per slice, qsc_obs_readings_fill's
-// walk: the list of a reading from the 33 segment bounds, k from the reading, the pixel from
-// perm), the C-format array by tile (one workgroup per tile: the bin from the tile's segment
-// bounds, the position from qlocal by tile_pos, the pixel from perm).  The occurrence index j of a
-// reading is its distance from the head of its run of equal keys, found by looking back along
-// the run (at most max_repeat long); both arrays are stable sorts of one list, so reading j of a
-// cell is the same reading in both and gets the same code.  S is read in position order [Pp][RP],
-// the order of both arrays' keys.
+// from its own keys, by the walks of qsc_obs_readings.cuh (see there): the S-format array by slice
+// (walk_s_slice: k from the reading, the pixel from perm), the C-format array by tile (walk_c_tile:
+// the position from qlocal by tile_pos, the pixel from perm).  The occurrence index j of a reading
+// is `occurrence`'s: reading j of a cell is the same reading in both arrays and gets the same
+// code.  S is read in position order [Pp][RP], the order of both arrays' keys.
 //
 // Listed cells (draw_list_kernel, qsc_draw_list).  A draw at cells given as lists (k, p, occurrence),
 // observed or not: one thread per query, the dense kernel's map value (natural planes) and the same
@@ -47,16 +43,17 @@
 #include "qsc_common.cuh"
 #include "qsc_newton.cuh"
 #include "qsc_obs_readings.cuh"
+#include "qsc_obs_tile.cuh"
 #include "qsc_philox.cuh"
 
 namespace {
 using namespace qsc;
 
-constexpr int kCells = 16;                 // cells per thread of the dense kernel
-constexpr int kTile = kBlock * kCells;     // cells per workgroup
+static_assert(kBlock == kTileBlock, "qsc_obs_tile.cuh");
 
 struct DrawKey {
-  uint32_t seed_lo, seed_hi, replicate;
+  SeedKey seed;
+  uint32_t replicate;
 };
 
 // the drawn code of one reading (the file header's rule); `keep` is the code it has
@@ -73,7 +70,7 @@ __device__ __forceinline__ int draw_code(float t, int keep, const float2* __rest
     }
     x = logf(tp);
   }
-  const float n = (float)(philox4x32_10_x0(k, p, j, key.replicate, key.seed_lo, key.seed_hi) >> 8);
+  const float n = (float)(philox4x32_10_x0(k, p, j, key.replicate, key.seed.lo, key.seed.hi) >> 8);
   float P1_, P2_;
   if (lk.nbins == 2) {
     float P0, P1;
@@ -116,39 +113,15 @@ __global__ void __launch_bounds__(kBlock) draw_codes_kernel(
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTile];
   __shared__ uint16_t list[kTile];
   __shared__ float ck[QSC_MAX_R];
-  __shared__ int nlist;
+  __shared__ int wcnt[65];
   QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);  // (its barrier is repeated below, after the other staging)
   const int k = blockIdx.x / tiles;
   const int p0 = (blockIdx.x - k * tiles) * kTile;
   const int np = min(kTile, P - p0);  // cells of this tile
   const int64_t row = (int64_t)k * P + p0;
   if (threadIdx.x < QSC_MAX_R) ck[threadIdx.x] = threadIdx.x < R ? C[(int64_t)threadIdx.x * K + k] : 0.0f;
-  if (threadIdx.x == 0) nlist = 0;
-  __syncthreads();
-  // the tile into LDS, the observed cells' offsets into the list
-  if (VEC) {
-    const int o = threadIdx.x * kCells;
-    if (o < np) {  // (P is a multiple of 16: a thread's 16 cells are all inside or all outside)
-      const uint4 v = *reinterpret_cast<const uint4*>(codes + row + o);
-      *reinterpret_cast<uint4*>(tile + o) = v;
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < kCells; ++i)
-        if (((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) != 0xFFu) list[atomicAdd(&nlist, 1)] = (uint16_t)(o + i);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < kCells; ++i) {
-      const int o = i * kBlock + threadIdx.x;
-      if (o < np) {
-        const uint8_t c = codes[row + o];
-        tile[o] = c;
-        if (c != 0xFFu) list[atomicAdd(&nlist, 1)] = (uint16_t)o;
-      }
-    }
-  }
-  __syncthreads();
-  const int nl = nlist;  // <= np <= kTile
+  // the tile into LDS, the observed cells' offsets into the list (its barriers cover ck too)
+  const int nl = stage_observed<VEC>(codes, row, np, tile, list, wcnt);  // <= np <= kTile
   int ninv = 0;
   for (int i = threadIdx.x; i < nl; i += kBlock) {
     const int o = list[i];
@@ -163,16 +136,7 @@ __global__ void __launch_bounds__(kBlock) draw_codes_kernel(
   }
   if (ninv) atomicAdd(invalid, ninv);
   __syncthreads();
-  if (VEC) {
-    const int o = threadIdx.x * kCells;
-    if (o < np) *reinterpret_cast<uint4*>(out + row + o) = *reinterpret_cast<const uint4*>(tile + o);
-  } else {
-#pragma unroll
-    for (int i = 0; i < kCells; ++i) {
-      const int o = i * kBlock + threadIdx.x;
-      if (o < np) out[row + o] = tile[o];
-    }
-  }
+  tile_store<VEC>(out, row, np, tile);
 }
 
 // t = S_pos[q] . c_k, r ascending (rows >= R of the position layout are zero and are not read)
@@ -192,30 +156,22 @@ __global__ void __launch_bounds__(kBlock) draw_rd_s_kernel(
     uint32_t* __restrict__ rd_out, int* __restrict__ invalid) {
   __shared__ int seg_sh[kWaves][QSC_SLICE + 1];
   QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   const int s = blockIdx.x * kWaves + wave;
-  const bool live = s < ns;
-  int* seg = seg_sh[wave];
-  if (live && lane <= QSC_SLICE) seg[lane] = seg_all[(int64_t)s * QSC_SLICE + lane];
-  __syncthreads();
-  if (!live) return;
-  const int lo = seg[0], hi = seg[QSC_SLICE];
   int ninv = 0;
-  for (int64_t e = (int64_t)lo + lane; e < hi && e < n; e += 64) {
-    const int l = seg_find(seg, QSC_SLICE, (int)e);
-    const uint32_t v = rd[e];
+  auto draw = [&](int64_t e, int l, uint32_t v, int e0) {
     const uint32_t k = v & kIdxMask;
     const int keep = (int)(v >> kIdxBits);
     const int64_t q = (int64_t)s * QSC_SLICE + l;
     const int p = perm[q];
-    uint32_t j = 0;  // readings of the same cell in front of this one
-    for (int64_t b = e - 1; b >= seg[l] && (rd[b] & kIdxMask) == k; --b) ++j;
+    const uint32_t j = occurrence(rd, e, e0, k);
     int code = keep;
     if (p >= 0 && p < P && (int)k < K && keep < lk.nbins)
       code = draw_code<LOGIT, LOG>(map_value(S_pos, q, RP, C, K, (int)k, R), keep, se, lk, k,
                                    (uint32_t)p, j, key, ninv);
     rd_out[e] = k | ((uint32_t)code << kIdxBits);
-  }
+  };
+  if (!walk_s_slice(rd, seg_all, n, ns, s, seg_sh[wave], draw)) return;
   // (every reading is counted once: by this array's kernel only)
   if (ninv) atomicAdd(invalid, ninv);
 }
@@ -231,18 +187,12 @@ __global__ void __launch_bounds__(kBlock) draw_rd_c_kernel(
   QSC_ENTRYWISE_STAGE(lk, E_.e[b_]);
   const int Kp = nks * 64;
   const int t = blockIdx.x;
-  for (int i = threadIdx.x; i <= Kp; i += blockDim.x) seg[i] = seg_all[(int64_t)t * Kp + i];
-  __syncthreads();
-  const int lo = seg[0], hi = seg[Kp];
   int ninv = 0;  // (counted by the S-format array's kernel)
-  for (int64_t e = (int64_t)lo + threadIdx.x; e < hi && e < n; e += blockDim.x) {
-    const int k = seg_find(seg, Kp, (int)e);
-    const uint32_t v = rd[e];
+  walk_c_tile(rd, seg_all, n, t, Kp, seg, [&](int64_t e, int k, uint32_t v, int e0) {
     const uint32_t ql = v & kIdxMask;
     const int keep = (int)(v >> kIdxBits);
     const int64_t q = tile_pos(t, (int)ql, nt);
-    uint32_t j = 0;
-    for (int64_t b = e - 1; b >= seg[k] && (rd[b] & kIdxMask) == ql; --b) ++j;
+    const uint32_t j = occurrence(rd, e, e0, ql);
     int code = keep;
     if (q >= 0 && q < Pp && k < K && keep < lk.nbins) {
       const int p = perm[q];
@@ -251,7 +201,7 @@ __global__ void __launch_bounds__(kBlock) draw_rd_c_kernel(
                                      (uint32_t)p, j, key, ninv);
     }
     rd_out[e] = ql | ((uint32_t)code << kIdxBits);
-  }
+  });
 }
 
 // ---- listed cells: one thread per query (k, p, occurrence) -> a code, 0xFF where none is drawn ----
@@ -277,13 +227,19 @@ __global__ void __launch_bounds__(kBlock) draw_list_kernel(
 
 inline DrawKey make_key(int64_t seed, int32_t replicate) {
   DrawKey k;
-  k.seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFu);
-  k.seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  k.seed = split_seed(seed);
   k.replicate = (uint32_t)replicate;
   return k;
 }
 
 }  // namespace
+
+// QSC_INFO_DISPATCH for LAUNCH(LOGIT, LOG, KIND): its third axis, the kind, is unused by the draws
+#define DRAW_DISPATCH(LAUNCH)                                     \
+  do {                                                            \
+    const int kind = INFO_EXPECTED;                               \
+    QSC_INFO_DISPATCH(LAUNCH);                                    \
+  } while (0)
 
 extern "C" {
 
@@ -298,10 +254,9 @@ QSC_API int qsc_draw_codes(const uint8_t* codes, int32_t K, int32_t P, const qsc
   Edges E;
   make_edges(m, &E);
   const DrawKey key = make_key(seed, replicate);
-  const bool vec = (P % kCells) == 0 && ((uintptr_t)codes % 16) == 0 && ((uintptr_t)codes_out % 16) == 0;
+  const bool vec = tile_vec_ok(P, codes, codes_out);
   const dim3 grid((unsigned)(tiles * K)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
-  const int kind = INFO_EXPECTED;  // (the dispatch macro's third axis: unused here)
 #define DRAW_LAUNCH_(LGT, LOGV, VC)                                                          \
   hipLaunchKernelGGL((draw_codes_kernel<LGT, LOGV, VC>), grid, blk, 0, hs, codes, K, P,      \
                      (int)tiles, S, C, R, lk, E, key, codes_out, invalid)
@@ -310,7 +265,7 @@ QSC_API int qsc_draw_codes(const uint8_t* codes, int32_t K, int32_t P, const qsc
     if (vec) DRAW_LAUNCH_(LGT, LOGV, true);  \
     else DRAW_LAUNCH_(LGT, LOGV, false);     \
   } while (0)
-  QSC_INFO_DISPATCH(DRAW_LAUNCH);
+  DRAW_DISPATCH(DRAW_LAUNCH);
 #undef DRAW_LAUNCH
 #undef DRAW_LAUNCH_
   QSC_CHECK_LAUNCH();
@@ -323,15 +278,11 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
                               int32_t replicate, void* packed_out, int32_t* invalid,
                               void* stream) {
   Dims dm;
-  if (!packed || !d || !perm || !S || !C || !packed_out || !invalid || packed == packed_out ||
-      !info_model_ok(m))
-    return QSC_EINVAL;
-  if (R < 1 || R > QSC_MAX_R || replicate < 0 || !n_ok(n) || d->nnz != n ||
-      d->nbins != m->nbounds - 1 || !dims_of(d->K, d->P, d->PT, &dm) || dm.Pp != d->Pp ||
-      dm.nt != d->ntiles || dm.nks != d->nks)
-    return QSC_EINVAL;
   Packed in, out;
-  if (packed_bytes < packed_carve((char*)packed, n, dm, &in)) return QSC_EINVAL;
+  if (!perm || !S || !C || !packed_out || !invalid || packed == packed_out || !info_model_ok(m) ||
+      R < 1 || R > QSC_MAX_R || replicate < 0 || !packed_of(packed, packed_bytes, n, d, &dm, &in) ||
+      d->nbins != m->nbounds - 1)
+    return QSC_EINVAL;
   packed_carve((char*)packed_out, n, dm, &out);
   // the C-format kernel's segment bounds (Kp + 1 ints) beside its edge table: the LDS a launch
   // gets without asking for more
@@ -346,7 +297,6 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
   // the segment tables (and the codes, replaced below)
   QSC_TRY(hipMemcpyAsync(packed_out, packed, packed_bytes, hipMemcpyDeviceToDevice, hs));
   const dim3 sg((unsigned)ceil_div(dm.ns, kWaves)), cg((unsigned)dm.nt), blk(kBlock);
-  const int kind = INFO_EXPECTED;
 #define DRAW_RD_LAUNCH(LGT, LOGV, KD)                                                           \
   do {                                                                                          \
     hipLaunchKernelGGL((draw_rd_s_kernel<LGT, LOGV>), sg, blk, 0, hs, in.s_rd, in.s_seg, n,     \
@@ -356,7 +306,7 @@ QSC_API int qsc_draw_readings(const void* packed, size_t packed_bytes, int64_t n
                        d->K, d->P, d->Pp, (int)dm.nt, (int)dm.nks, RP, perm, S, C, R, lk, E,    \
                        key, out.c_rd);                                                          \
   } while (0)
-  QSC_INFO_DISPATCH(DRAW_RD_LAUNCH);
+  DRAW_DISPATCH(DRAW_RD_LAUNCH);
 #undef DRAW_RD_LAUNCH
   QSC_CHECK_LAUNCH();
   return QSC_OK;
@@ -376,14 +326,14 @@ QSC_API int qsc_draw_list(const int32_t* k, const int32_t* p, const int32_t* occ
   const DrawKey key = make_key(seed, replicate);
   const dim3 grid((unsigned)ceil_div(n, kBlock)), blk(kBlock);
   hipStream_t hs = STREAM(stream);
-  const int kind = INFO_EXPECTED;
 #define DRAW_LIST_LAUNCH(LGT, LOGV, KD)                                                       \
   hipLaunchKernelGGL((draw_list_kernel<LGT, LOGV>), grid, blk, 0, hs, k, p, occ, n, K, P, S, \
                      C, R, lk, E, key, code, invalid)
-  QSC_INFO_DISPATCH(DRAW_LIST_LAUNCH);
+  DRAW_DISPATCH(DRAW_LIST_LAUNCH);
 #undef DRAW_LIST_LAUNCH
   QSC_CHECK_LAUNCH();
   return QSC_OK;
 }
 
 }  // extern "C"
+#undef DRAW_DISPATCH

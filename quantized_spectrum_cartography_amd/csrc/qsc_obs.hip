@@ -35,11 +35,6 @@ __global__ void iota_kernel(int* __restrict__ v, int n) {
   if (i < n) v[i] = i;
 }
 
-__global__ void fill_int_kernel(int* __restrict__ v, int n, int val) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = val;
-}
-
 // S-format slice widths: QSC_SLICE * round4(max count in the slice)
 __global__ void __launch_bounds__(kBlock) s_width_kernel(const int* __restrict__ perm,
                                                          const int* __restrict__ cnt, int P,
@@ -214,8 +209,6 @@ struct LayoutWs {
   size_t cub_bytes;
 };
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t cub_scan_bytes(int n) {
   size_t b = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, n);
@@ -265,11 +258,7 @@ QSC_API int qsc_obs_order(const int32_t* cnt, int32_t P, int32_t Pp, int32_t* pe
   hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(cub, cub_b, cnt, keys_out, vals_in,
                                                               perm, P, 0, 32, s);
   if (e != hipSuccess) return (int)e;
-  if (Pp > P) {
-    hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)ceil_div(Pp - P, kBlock)), dim3(kBlock), 0,
-                       s, perm + P, Pp - P, -1);
-    QSC_CHECK_LAUNCH();
-  }
+  if (Pp > P) QSC_TRY(hipMemsetAsync(perm + P, 0xFF, (size_t)(Pp - P) * sizeof(int), s));  // -1
   return QSC_OK;
 }
 

@@ -197,11 +197,6 @@ size_t merge_carve(char* b, int64_t m, int32_t K, int32_t P, int32_t PT, MergeWs
   return (size_t)(p - b);
 }
 
-bool desc_dims(const qsc_obs_desc* d, Dims* dm) {
-  return d && dims_of(d->K, d->P, d->PT, dm) && dm->Pp == d->Pp && dm->nt == d->ntiles &&
-         dm->nks == d->nks;
-}
-
 }  // namespace
 
 extern "C" {
@@ -211,13 +206,10 @@ QSC_API int qsc_obs_cell_counts(const uint8_t* codes, const void* packed, size_t
                                 const int32_t* k, const int32_t* p, int64_t m, int32_t* cnt,
                                 void* stream) {
   Dims dm;
-  if (!k || !p || !cnt || !n_ok(m) || !desc_dims(d, &dm)) return QSC_EINVAL;
   Packed pk = {};
-  if (!codes) {
-    if (!packed || !iperm || !n_ok(n) || d->nnz != n ||
-        packed_bytes < packed_carve((char*)packed, n, dm, &pk))
-      return QSC_EINVAL;
-  }
+  if (!k || !p || !cnt || !n_ok(m)) return QSC_EINVAL;
+  if (codes ? !desc_dims(d, &dm) : !iperm || !packed_of(packed, packed_bytes, n, d, &dm, &pk))
+    return QSC_EINVAL;
   hipLaunchKernelGGL(cell_counts_kernel, dim3((unsigned)ceil_div(m, kBlock)), dim3(kBlock), 0,
                      STREAM(stream), codes, pk.s_rd, pk.s_seg, iperm, n, d->K, d->P, d->Pp, k, p,
                      m, cnt);
@@ -249,18 +241,16 @@ QSC_API int qsc_obs_readings_merge(const void* packed, size_t packed_bytes, int6
                                    size_t ws_bytes, qsc_obs_desc* desc, int32_t* max_repeat,
                                    void* stream) {
   Dims dm;
-  if (!packed || !perm || !k || !p || !code || !cnt || !s_width || !s_off || !c_width || !c_off ||
-      !c_kmap || !packed_out || packed_out == packed || !ws || !desc || !max_repeat ||
-      !merge_ok(n, m) || (code_bytes != 1 && code_bytes != 4) || !desc_dims(d, &dm) ||
-      d->nnz != n || d->nbins < 1 || d->nbins > QSC_MAX_BOUNDS - 1)
+  Packed in, out;
+  MergeWs w;
+  if (!perm || !k || !p || !code || !cnt || !s_width || !s_off || !c_width || !c_off || !c_kmap ||
+      !packed_out || packed_out == packed || !ws || !desc || !max_repeat || !merge_ok(n, m) ||
+      (code_bytes != 1 && code_bytes != 4) || !packed_of(packed, packed_bytes, n, d, &dm, &in) ||
+      d->nbins < 1 || d->nbins > QSC_MAX_BOUNDS - 1)
     return QSC_EINVAL;
   const int32_t K = d->K, P = d->P, PT = d->PT, nbins = d->nbins;
   if (!rd_layout_fits(K, P, PT)) return QSC_EINVAL;
-  Packed in, out;
-  MergeWs w;
-  if (packed_bytes < packed_carve((char*)packed, n, dm, &in) ||
-      packed_out_bytes < packed_carve((char*)packed_out, n + m, dm, &out))
-    return QSC_EINVAL;
+  if (packed_out_bytes < packed_carve((char*)packed_out, n + m, dm, &out)) return QSC_EINVAL;
   const size_t need = merge_carve((char*)ws, m, K, P, PT, &w);
   if (!need || ws_bytes < need) return QSC_EINVAL;
   const int Pp = (int)dm.Pp, nb = (int)dm.nb;

@@ -3,6 +3,8 @@
 // writes them and fills the entry formats from them), qsc_draw.hip (which redraws their codes),
 // qsc_obs_select.hip (which exports the kept ones as lists) and qsc_obs_append.hip (which merges a
 // sorted batch into them, between the layout's own stages: declared at the end of this file).
+// Written here once for all of them: the occurrence number of a sorted reading (occurrence), the
+// walks of the two arrays (walk_s_slice, walk_c_tile), the check of a caller's `packed` (packed_of).
 //
 // A sorted reading is  idx | code << 24  (idx = k or qlocal < 2^24, the wide format's own bound).
 #pragma once
@@ -14,8 +16,6 @@ using namespace qsc;
 constexpr int kIdxBits = 24;
 constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1;
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the list l of `nl` contiguous segments that holds sorted reading e: seg[l] <= e < seg[l + 1]
 // (seg[0] <= e < seg[nl] on entry; empty segments are stepped over)
 __device__ __forceinline__ int seg_find(const int* seg, int nl, int e) {
@@ -25,6 +25,55 @@ __device__ __forceinline__ int seg_find(const int* seg, int nl, int e) {
     if (seg[mid] <= e) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+// The occurrence number j of sorted reading e (index idx, its list starting at seg_lo): the
+// readings of the same cell in front of it, counted by looking back along the run of equal indices
+// (at most max_repeat long).  Both arrays are stable sorts of one list, so reading j of a cell is
+// the same reading in both; the Philox counter of every draw and of every keep decision hangs on
+// this j.  A run may begin before the caller's chunk: the reads are global.
+__device__ __forceinline__ uint32_t occurrence(const uint32_t* __restrict__ rd, int64_t e,
+                                               int seg_lo, uint32_t idx) {
+  uint32_t j = 0;
+  for (int64_t b = e - 1; b >= seg_lo && (rd[b] & kIdxMask) == idx; --b) ++j;
+  return j;
+}
+
+// The walk of slice s of the S-format sorted array by one wave: the slice's 32 lists are one
+// contiguous run of rd, read coalesced; `seg` (this wave's QSC_SLICE + 1 ints of LDS) gets their
+// bounds.  body(e, l, rd[e], seg[l]) for every reading e of the slice, l its list.  Every wave of
+// the workgroup calls it (one barrier); -> false for a wave past the last slice, which ends there.
+template <typename Body>
+__device__ __forceinline__ bool walk_s_slice(const uint32_t* __restrict__ rd,
+                                             const int* __restrict__ seg_all, int64_t n, int ns,
+                                             int s, int* seg, Body&& body) {
+  const int lane = threadIdx.x & 63;
+  const bool live = s < ns;
+  if (live && lane <= QSC_SLICE) seg[lane] = seg_all[(int64_t)s * QSC_SLICE + lane];
+  __syncthreads();
+  if (!live) return false;
+  const int lo = seg[0], hi = seg[QSC_SLICE];
+  for (int64_t e = (int64_t)lo + lane; e < hi && e < n; e += 64) {
+    const int l = seg_find(seg, QSC_SLICE, (int)e);
+    body(e, l, rd[e], seg[l]);
+  }
+  return true;
+}
+
+// The walk of tile t of the C-format sorted array by one workgroup: the tile's Kp bin lists (bins
+// in k order) are one contiguous run of rd; `seg` (Kp + 1 ints of LDS) receives their bounds.
+// body(e, k, rd[e], seg[k]) for every reading e of the tile, k its bin.  One barrier.
+template <typename Body>
+__device__ __forceinline__ void walk_c_tile(const uint32_t* __restrict__ rd,
+                                            const int* __restrict__ seg_all, int64_t n, int t,
+                                            int Kp, int* seg, Body&& body) {
+  for (int i = threadIdx.x; i <= Kp; i += blockDim.x) seg[i] = seg_all[(int64_t)t * Kp + i];
+  __syncthreads();
+  const int lo = seg[0], hi = seg[Kp];
+  for (int64_t e = (int64_t)lo + threadIdx.x; e < hi && e < n; e += blockDim.x) {
+    const int k = seg_find(seg, Kp, (int)e);
+    body(e, k, rd[e], seg[k]);
+  }
 }
 
 // shapes both calls derive from (K, P, PT)
@@ -68,6 +117,19 @@ inline size_t packed_carve(char* b, int64_t n, const Dims& d, Packed* pk) {
 }
 
 inline bool n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
+
+// a caller's descriptor against the shapes its (K, P, PT) give -> *dm
+inline bool desc_dims(const qsc_obs_desc* d, Dims* dm) {
+  return d && dims_of(d->K, d->P, d->PT, dm) && dm->Pp == d->Pp && dm->nt == d->ntiles &&
+         dm->nks == d->nks;
+}
+// ... and a caller's `packed` of n readings against it -> *pk.  counted: n is d->nnz, i.e. every
+// reading has a position (the fill alone also takes a layout where some have none)
+inline bool packed_of(const void* packed, size_t packed_bytes, int64_t n, const qsc_obs_desc* d,
+                      Dims* dm, Packed* pk, bool counted = true) {
+  return packed && n_ok(n) && desc_dims(d, dm) && (!counted || d->nnz == n) &&
+         packed_bytes >= packed_carve((char*)packed, n, *dm, pk);
+}
 
 }  // namespace
 

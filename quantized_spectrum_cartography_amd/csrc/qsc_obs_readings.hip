@@ -49,11 +49,6 @@ __global__ void __launch_bounds__(kBlock) rd_count_kernel(const int* __restrict_
     atomicAdd(bad, 1);
 }
 
-__global__ void rd_fill_int_kernel(int* __restrict__ v, int64_t n, int val) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) v[i] = val;
-}
-
 // iperm[perm[q]] = q; poscnt[q] = readings of position q (0 for padding positions)
 __global__ void __launch_bounds__(kBlock) rd_positions_kernel(const int* __restrict__ perm,
                                                               const int* __restrict__ cnt, int P,
@@ -179,9 +174,8 @@ __global__ void __launch_bounds__(kBlock) rd_c_order_kernel(const int* __restric
   if (t == 0 && threadIdx.x == 0) sizes[(int64_t)gridDim.x * nks] = 0;  // the scan's total slot
 }
 
-// S-format fill, one wave per slice: the slice's 32 lists are one contiguous run of the sorted
-// readings, read coalesced; each reading finds its list in the 33 segment bounds (LDS) and is
-// stored at its chunked slot.  Then the slice's slots are swept in address order for the pads.
+// S-format fill, one wave per slice (walk_s_slice, qsc_obs_readings.cuh): each reading is stored
+// at its chunked slot.  Then the slice's slots are swept in address order for the pads.
 template <typename E>
 __global__ void __launch_bounds__(kBlock) rd_s_fill_kernel(const uint32_t* __restrict__ rd,
                                                            const int* __restrict__ seg_all,
@@ -192,21 +186,15 @@ __global__ void __launch_bounds__(kBlock) rd_s_fill_kernel(const uint32_t* __res
   __shared__ int seg_sh[kBlock / 64][QSC_SLICE + 1];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int s = blockIdx.x * (kBlock / 64) + wave;
-  const bool live = s < ns;
   int* seg = seg_sh[wave];
-  if (live && lane <= QSC_SLICE) seg[lane] = seg_all[(int64_t)s * QSC_SLICE + lane];
-  __syncthreads();
-  if (!live) return;
-  const int W = width[s];
-  const int64_t base = off[s];
-  const int lo = seg[0], hi = seg[QSC_SLICE];
-  for (int64_t e = (int64_t)lo + lane; e < hi && e < n; e += 64) {
-    const int l = seg_find(seg, QSC_SLICE, (int)e);
-    const int j = (int)e - seg[l];
-    if (j >= W) continue;  // (cannot happen for consistent tables; keeps the store in the slice)
-    const uint32_t v = rd[e];
-    ent[slot(base, QSC_SLICE, l, j)] = entry_of<E>(v & kIdxMask, v >> kIdxBits, sr, K);
-  }
+  const int W = s < ns ? width[s] : 0;
+  const int64_t base = s < ns ? off[s] : 0;
+  auto store = [&](int64_t e, int l, uint32_t v, int e0) {
+    const int j = (int)e - e0;
+    // (j >= W cannot happen for consistent tables; the test keeps the store in the slice)
+    if (j < W) ent[slot(base, QSC_SLICE, l, j)] = entry_of<E>(v & kIdxMask, v >> kIdxBits, sr, K);
+  };
+  if (!walk_s_slice(rd, seg_all, n, ns, s, seg, store)) return;
   const E pad = pad_of<E>(sr, K);
   for (int64_t o = lane; o < (int64_t)W * QSC_SLICE; o += 64) {  // W * 32 may pass 2^31
     const int l = (int)(o >> 2) & (QSC_SLICE - 1), j = (int)(o / (QSC_SLICE * 4)) * 4 + (int)(o & 3);
@@ -214,10 +202,9 @@ __global__ void __launch_bounds__(kBlock) rd_s_fill_kernel(const uint32_t* __res
   }
 }
 
-// C-format fill, one block per tile: the tile's Kp bin lists are one contiguous run of the
-// sorted readings (bins in k order), read coalesced; each reading finds its bin in the tile's
-// segment bounds (LDS), the bin's place in the count-sorted order in kinv, and is stored at its
-// chunked slot.  Then every (tile, k-slice) block is swept in address order for the pads.
+// C-format fill, one block per tile (walk_c_tile, qsc_obs_readings.cuh): each reading finds its
+// bin's place in the count-sorted order in kinv and is stored at its chunked slot.  Then every
+// (tile, k-slice) block is swept in address order for the pads.
 template <typename E>
 __global__ void __launch_bounds__(kBlock) rd_c_fill_kernel(
     const uint32_t* __restrict__ rd, const int* __restrict__ seg_all, int64_t n, int K, int PT,
@@ -226,19 +213,14 @@ __global__ void __launch_bounds__(kBlock) rd_c_fill_kernel(
   extern __shared__ int seg[];  // [Kp + 1]
   const int Kp = nks * 64;
   const int t = blockIdx.x;
-  for (int i = threadIdx.x; i <= Kp; i += blockDim.x) seg[i] = seg_all[(int64_t)t * Kp + i];
-  __syncthreads();
-  const int lo = seg[0], hi = seg[Kp];
-  for (int64_t e = (int64_t)lo + threadIdx.x; e < hi && e < n; e += blockDim.x) {
-    const int k = seg_find(seg, Kp, (int)e);
-    const int j = (int)e - seg[k];
+  walk_c_tile(rd, seg_all, n, t, Kp, seg, [&](int64_t e, int k, uint32_t v, int e0) {
+    const int j = (int)e - e0;
     const int rank = kinv[(int64_t)t * Kp + k];
-    if (rank < 0 || rank >= Kp) continue;
+    if (rank < 0 || rank >= Kp) return;
     const int64_t wi = (int64_t)t * nks + (rank >> 6);
-    if (j >= width[wi]) continue;  // (cannot happen for consistent tables)
-    const uint32_t v = rd[e];
+    if (j >= width[wi]) return;  // (cannot happen for consistent tables)
     ent[slot(off[wi], 64, rank & 63, j)] = entry_of<E>(v & kIdxMask, v >> kIdxBits, sr, PT);
-  }
+  });
   const E pad = pad_of<E>(sr, PT);
   for (int ks = 0; ks < nks; ++ks) {
     const int64_t wi = (int64_t)t * nks + ks;
@@ -346,9 +328,7 @@ int rd_layout_positions(const RdWs& w, int32_t K, int32_t P, int32_t PT, const i
   Dims d;
   if (!dims_of(K, P, PT, &d)) return QSC_EINVAL;
   const int Pp = (int)d.Pp, ns = (int)d.ns;
-  hipLaunchKernelGGL(rd_fill_int_kernel, dim3((unsigned)ceil_div(P, kBlock)), dim3(kBlock), 0, s,
-                     w.iperm, (int64_t)P, -1);
-  QSC_CHECK_LAUNCH();
+  QSC_TRY(hipMemsetAsync(w.iperm, 0xFF, (size_t)P * sizeof(int), s));  // -1: no position
   hipLaunchKernelGGL(rd_positions_kernel, dim3((unsigned)ceil_div(Pp + 1, kBlock)), dim3(kBlock),
                      0, s, perm, cnt, P, Pp, w.iperm, w.poscnt);
   QSC_CHECK_LAUNCH();
@@ -509,13 +489,11 @@ QSC_API int qsc_obs_readings_fill(const void* packed, size_t packed_bytes, int64
                                   const int64_t* c_off, const int32_t* c_kmap, void* s_entries,
                                   void* c_entries, void* stream) {
   Dims dm;
-  if (!d || !packed || !s_width || !s_off || !c_width || !c_off || !c_kmap || !s_entries ||
-      !c_entries || !n_ok(n) || d->s_entries < QSC_ENTRY_TAIL || d->c_entries < QSC_ENTRY_TAIL ||
-      !dims_of(d->K, d->P, d->PT, &dm) || dm.Pp != d->Pp || dm.nt != d->ntiles ||
-      dm.nks != d->nks)
-    return QSC_EINVAL;
   Packed pk;
-  if (packed_bytes < packed_carve((char*)packed, n, dm, &pk)) return QSC_EINVAL;
+  if (!s_width || !s_off || !c_width || !c_off || !c_kmap || !s_entries || !c_entries ||
+      !packed_of(packed, packed_bytes, n, d, &dm, &pk, /*counted=*/false) ||
+      d->s_entries < QSC_ENTRY_TAIL || d->c_entries < QSC_ENTRY_TAIL)
+    return QSC_EINVAL;
   // signed rows: narrow entries, every row index (up to the last pad row) representable
   const int sr = d->rowfmt == 1 ? 1 : 0;
   if (d->rowfmt != 0 && (d->rowfmt != 1 || d->wide || (int64_t)sr_rows(d->K) > 0x10000 ||

@@ -9,48 +9,40 @@
 // hi = 2^24, invert = 0 the range rule is off and no Philox is evaluated.
 //
 // Dense codes are worked on as one flat array of K P cells in chunks of kTile = 4096 (flat order
-// is (k, p) ascending).  A workgroup stages its chunk in LDS (one 16-byte load per thread where P
-// and the pointers allow it, byte loads otherwise) and lists the observed cells' offsets in
-// ascending order, so that the rule -- ten Philox rounds -- runs on full waves of observed cells
-// only (about one cell in ten is observed).
+// is (k, p) ascending), staged as qsc_obs_tile.cuh's dense tile (see there), so that the rule --
+// ten Philox rounds -- runs on full waves of observed cells only.
 //
 // The exports are stable stream compactions in three steps: (1) the kept count of every chunk,
-// (2) one exclusive scan of the chunk counts, (3) the rule again, an in-chunk scan and the scatter.
-// The in-chunk scan is by ballot and popcount: element i * 256 + tid of a chunk is bit i of thread
-// tid's mask; the popcounts of the ROUNDS x 4 (round, wave) ballots -- at most 64 numbers -- are
-// scanned by one wave64 with shuffles, and an element's place is its (round, wave) prefix plus the
-// popcount of its ballot below its lane.  No atomics decide a position: the output bytes are a
-// function of the input.
+// (2) one exclusive scan of the chunk counts, (3) the rule again, an in-chunk scan (block_scan /
+// scan_pos, see qsc_obs_tile.cuh) and the scatter.  No atomics decide a position: the output bytes
+// are a function of the input.
 //
 // Readings (export_rd_kernel) are read from the S-format sorted array of `packed` in chunks of
 // kRdChunk = 1024: the position of a reading from the segment table (the chunk's first and last
 // position are searched once, every reading then searches between them), p = perm[position], j_occ
-// by looking back along the run of equal k inside the position's own segment (global reads: a run
-// may begin in the chunk before).  Order: (position, k, occurrence), the sorted array's own.
+// by occurrence (see qsc_obs_readings.cuh).  Order: (position, k, occurrence), the sorted array's.
 //
 // Stream-ordered, no allocation; integer atomics for *kept only.
 #include <hipcub/hipcub.hpp>
 
 #include "qsc_common.cuh"
 #include "qsc_obs_readings.cuh"
+#include "qsc_obs_tile.cuh"
 #include "qsc_philox.cuh"
 
 namespace {
 using namespace qsc;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kCells = 16;                    // cells per thread of the dense kernels
-constexpr int kTile = kBlock * kCells;        // cells per workgroup (QSC_EXPORT_CHUNK_CODES)
+constexpr int kBlock = kTileBlock;
 constexpr int kRdRounds = 4;
-constexpr int kRdChunk = kBlock * kRdRounds;  // readings per workgroup (QSC_EXPORT_CHUNK_READINGS)
-static_assert(kTile == QSC_EXPORT_CHUNK_CODES && kRdChunk == QSC_EXPORT_CHUNK_READINGS, "qsc.h");
-static_assert(kCells * kWaves <= 64, "one wave64 scans the (round, wave) counts");
+constexpr int kRdChunk = kBlock * kRdRounds;  // readings per workgroup
+static_assert(kRdChunk == QSC_EXPORT_CHUNK_READINGS, "qsc.h");
 
 struct Rule {
   const uint8_t* keep_pixel;  // [P] or null
   const uint8_t* keep_bin;    // [K] or null
-  uint32_t seed_lo, seed_hi, lo, hi;
+  SeedKey seed;
+  uint32_t lo, hi;
   int invert, ranged;         // ranged = 0: lo = 0, hi = 2^24, invert = 0
 };
 
@@ -58,74 +50,8 @@ __device__ __forceinline__ bool keep(const Rule& r, uint32_t k, uint32_t p, uint
   if (r.keep_pixel && !r.keep_pixel[p]) return false;
   if (r.keep_bin && !r.keep_bin[k]) return false;
   if (!r.ranged) return true;
-  const uint32_t u = philox4x32_10_x0(k, p, j, 0x80000000u, r.seed_lo, r.seed_hi) >> 8;
+  const uint32_t u = philox4x32_10_x0(k, p, j, 0x80000000u, r.seed.lo, r.seed.hi) >> 8;
   return (u >= r.lo && u < r.hi) != (r.invert != 0);
-}
-
-// Exclusive scan of the selected elements of a chunk: bit i of `mask` selects element
-// i * kBlock + tid.  Leaves the (round, wave) prefixes in wcnt[0 .. 63] and the total in wcnt[64]
-// (which is returned).  Every thread of the workgroup calls it.
-template <int ROUNDS>
-__device__ __forceinline__ int block_scan(uint32_t mask, int* wcnt) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < ROUNDS; ++i) {
-    const unsigned long long b = __ballot((mask >> i) & 1u);
-    if (lane == 0) wcnt[i * kWaves + wave] = __popcll(b);
-  }
-  __syncthreads();
-  if (wave == 0) {
-    const int v = lane < ROUNDS * kWaves ? wcnt[lane] : 0;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(inc, d);
-      if (lane >= d) inc += u;
-    }
-    wcnt[lane] = inc - v;
-    if (lane == 63) wcnt[64] = inc;
-  }
-  __syncthreads();
-  return wcnt[64];
-}
-// the place of element (round i, this thread) among the selected ones; all threads call it
-__device__ __forceinline__ int scan_pos(uint32_t mask, int i, const int* wcnt) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned long long b = __ballot((mask >> i) & 1u);
-  return wcnt[i * kWaves + wave] + __popcll(b & ((1ull << lane) - 1ull));
-}
-
-// The chunk [c0, c0 + nc) of the flat codes into `tile`, the offsets of its observed cells into
-// `list`, ascending.  -> their number.  Ends with a barrier.
-template <bool VEC>
-__device__ __forceinline__ int stage_observed(const uint8_t* __restrict__ codes, int64_t c0, int nc,
-                                              uint8_t* tile, uint16_t* list, int* wcnt) {
-  if (VEC) {
-    const int o = threadIdx.x * kCells;
-    // (the cell count is a multiple of 16: a thread's 16 cells are all inside or all outside)
-    if (o < nc) *reinterpret_cast<uint4*>(tile + o) = *reinterpret_cast<const uint4*>(codes + c0 + o);
-  } else {
-#pragma unroll
-    for (int i = 0; i < kCells; ++i) {
-      const int o = i * kBlock + threadIdx.x;
-      if (o < nc) tile[o] = codes[c0 + o];
-    }
-  }
-  __syncthreads();
-  uint32_t mask = 0;
-#pragma unroll
-  for (int i = 0; i < kCells; ++i) {
-    const int o = i * kBlock + threadIdx.x;
-    if (o < nc && tile[o] != 0xFFu) mask |= 1u << i;
-  }
-  const int nl = block_scan<kCells>(mask, wcnt);
-#pragma unroll
-  for (int i = 0; i < kCells; ++i) {
-    const int pos = scan_pos(mask, i, wcnt);
-    if ((mask >> i) & 1u) list[pos] = (uint16_t)(i * kBlock + threadIdx.x);
-  }
-  __syncthreads();
-  return nl;
 }
 
 // (k, p) of the cell at offset o of a chunk whose first cell is (k0, p0): the chunk's start is
@@ -163,16 +89,7 @@ __global__ void __launch_bounds__(kBlock) select_codes_kernel(
   if (nk) atomicAdd(&nkept, nk);
   __syncthreads();
   if (threadIdx.x == 0 && nkept) atomicAdd(kept, (unsigned long long)nkept);
-  if (VEC) {
-    const int o = threadIdx.x * kCells;
-    if (o < nc) *reinterpret_cast<uint4*>(out + c0 + o) = *reinterpret_cast<const uint4*>(tile + o);
-  } else {
-#pragma unroll
-    for (int i = 0; i < kCells; ++i) {
-      const int o = i * kBlock + threadIdx.x;
-      if (o < nc) out[c0 + o] = tile[o];
-    }
-  }
+  tile_store<VEC>(out, c0, nc, tile);
 }
 
 // ---- dense export: COUNT: counts[chunk] = kept cells; else scatter them from offs[chunk] on ----
@@ -216,12 +133,6 @@ __global__ void __launch_bounds__(kBlock) export_codes_kernel(
   }
 }
 
-// the position q in [lo, hi) of sorted reading e: seg[q] <= e < seg[q + 1] (seg[lo] <= e < seg[hi]
-// on entry; empty positions are stepped over)
-__device__ __forceinline__ int pos_find(const int* __restrict__ seg, int lo, int hi, int e) {
-  return lo + seg_find(seg + lo, hi - lo, e);
-}
-
 // ---- readings export, from the S-format sorted array ----
 template <bool COUNT>
 __global__ void __launch_bounds__(kBlock) export_rd_kernel(
@@ -234,8 +145,8 @@ __global__ void __launch_bounds__(kBlock) export_rd_kernel(
   const int64_t e0 = (int64_t)blockIdx.x * kRdChunk;
   const int ne = (int)min((int64_t)kRdChunk, n - e0);
   // (seg[0] = 0 <= e and seg[Pp] = n > e for every reading e)
-  if (threadIdx.x == 0) qr[0] = pos_find(seg, 0, Pp, (int)e0);
-  if (threadIdx.x == 64) qr[1] = pos_find(seg, 0, Pp, (int)(e0 + ne - 1));
+  if (threadIdx.x == 0) qr[0] = seg_find(seg, Pp, (int)e0);
+  if (threadIdx.x == 64) qr[1] = seg_find(seg, Pp, (int)(e0 + ne - 1));
   __syncthreads();
   const int qlo = qr[0], qhi = qr[1];
   uint32_t mask = 0;
@@ -246,12 +157,11 @@ __global__ void __launch_bounds__(kBlock) export_rd_kernel(
     kk[i] = pp[i] = cc[i] = 0;
     if (idx < ne) {
       const int64_t e = e0 + idx;
-      const int q = pos_find(seg, qlo, qhi + 1, (int)e);
+      const int q = qlo + seg_find(seg + qlo, qhi + 1 - qlo, (int)e);
       const uint32_t v = rd[e];
       const uint32_t k = v & kIdxMask;
       const int p = perm[q];
-      uint32_t j = 0;  // readings of the same cell in front of this one
-      for (int64_t b = e - 1; b >= seg[q] && (rd[b] & kIdxMask) == k; --b) ++j;
+      const uint32_t j = occurrence(rd, e, seg[q], k);
       kk[i] = (int)k;
       pp[i] = p;
       cc[i] = (int)(v >> kIdxBits);
@@ -280,8 +190,7 @@ inline bool make_rule(const uint8_t* keep_pixel, const uint8_t* keep_bin, int64_
   if (lo < 0 || hi < lo || hi > (1 << 24) || (invert != 0 && invert != 1)) return false;
   r->keep_pixel = keep_pixel;
   r->keep_bin = keep_bin;
-  r->seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFu);
-  r->seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  r->seed = split_seed(seed);
   r->lo = (uint32_t)lo;
   r->hi = (uint32_t)hi;
   r->invert = invert;
@@ -340,7 +249,7 @@ QSC_API int qsc_select_codes(const uint8_t* codes, int32_t K, int32_t P, const u
     return QSC_EINVAL;
   const int64_t total = (int64_t)K * P, chunks = ceil_div(total, kTile);
   if (chunks >= ((int64_t)1 << 31)) return QSC_EINVAL;
-  const bool vec = (P % kCells) == 0 && ((uintptr_t)codes % 16) == 0 && ((uintptr_t)out % 16) == 0;
+  const bool vec = tile_vec_ok(P, codes, out);
   const dim3 grid((unsigned)chunks), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   if (vec)
@@ -370,7 +279,7 @@ QSC_API int qsc_export_codes(const uint8_t* codes, int32_t K, int32_t P, const u
   const int64_t total = (int64_t)K * P, chunks = ceil_div(total, kTile);
   ExportWs w;
   if (ws_bytes < export_carve((char*)ws, chunks, &w)) return QSC_EINVAL;
-  const bool vec = (P % kCells) == 0 && ((uintptr_t)codes % 16) == 0;
+  const bool vec = tile_vec_ok(P, codes);
   const dim3 grid((unsigned)chunks), blk(kBlock);
   hipStream_t hs = STREAM(stream);
   QSC_TRY(hipMemsetAsync(w.counts + chunks, 0, 8, hs));
@@ -395,12 +304,11 @@ QSC_API int qsc_export_readings(const void* packed, size_t packed_bytes, int64_t
                                 size_t ws_bytes, void* stream) {
   Rule rule;
   Dims dm;
-  if (!packed || !d || !perm || !k_out || !p_out || !code_out || !n_out || !ws || !n_ok(n) ||
-      d->nnz != n || !dims_of(d->K, d->P, d->PT, &dm) || dm.Pp != d->Pp || dm.nt != d->ntiles ||
-      dm.nks != d->nks || !make_rule(keep_pixel, keep_bin, seed, lo, hi, invert, &rule))
-    return QSC_EINVAL;
   Packed in;
-  if (packed_bytes < packed_carve((char*)packed, n, dm, &in)) return QSC_EINVAL;
+  if (!perm || !k_out || !p_out || !code_out || !n_out || !ws ||
+      !packed_of(packed, packed_bytes, n, d, &dm, &in) ||
+      !make_rule(keep_pixel, keep_bin, seed, lo, hi, invert, &rule))
+    return QSC_EINVAL;
   const int64_t chunks = ceil_div(n, kRdChunk);
   ExportWs w;
   if (ws_bytes < export_carve((char*)ws, chunks, &w)) return QSC_EINVAL;

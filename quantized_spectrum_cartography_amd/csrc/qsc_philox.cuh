@@ -6,6 +6,12 @@
 
 namespace {
 
+// the generator's key: the two halves of the ABI's 64-bit seed
+struct SeedKey { uint32_t lo, hi; };
+inline SeedKey split_seed(int64_t seed) {
+  return {(uint32_t)((uint64_t)seed & 0xFFFFFFFFu), (uint32_t)((uint64_t)seed >> 32)};
+}
+
 // Philox4x32-10 (Salmon et al., SC'11): the first word of the output block
 __device__ __forceinline__ uint32_t philox4x32_10_x0(uint32_t c0, uint32_t c1, uint32_t c2,
                                                      uint32_t c3, uint32_t k0, uint32_t k1) {

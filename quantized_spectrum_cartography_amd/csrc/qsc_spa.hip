@@ -566,8 +566,6 @@ SyrkPlan syrk_plan(int K, int64_t P) {
   return pl;
 }
 
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {

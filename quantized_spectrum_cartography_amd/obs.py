@@ -21,6 +21,17 @@ def ctypes_copy(dst, src):
         setattr(dst, name, getattr(src, name))
 
 
+def _seed64(seed):  # an int seed in [-2^63, 2^64) as a signed 64-bit value
+    if not -2 ** 63 <= seed < 2 ** 64:
+        raise ValueError("seed must fit 64 bits, got %r" % (seed,))
+    return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+
+def _check_perm(perm):  # the pixel order of a derived packing: this object's, or by the new counts
+    if perm not in ("keep", "fresh"):
+        raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+
+
 def default_tile(P, R, K):
     """C-pass pixel tile (positions, a power of two in [256, 1024]; 128 at rank 16 when LDS
     requires it).
@@ -402,9 +413,8 @@ class Observations:
 
     @staticmethod
     def check_resample(loss, K, I, J, S, C, seed=0, replicate=0):
-        """Host-side checks of resample's arguments, before any device call: a likelihood, S
-        (R,1,I,J) or (R,I,J) (or (R,I J)), C (R,K), 1 <= R <= 16, seed in [-2^63, 2^64),
-        0 <= replicate < 2^31.  -> (R, seed as a signed 64-bit value).  Raises ValueError."""
+        """Host-side checks of resample's arguments (ValueError), before any device call: a
+        likelihood, S (R,1,I,J), (R,I,J) or (R,I J), C (R,K), R <= 16, replicate.  -> R, seed64."""
         if loss == "squared":
             raise ValueError('loss="squared" is not a likelihood: there is nothing to draw from')
         for name, t in (("S", S), ("C", C)):
@@ -418,12 +428,9 @@ class Observations:
                              % (I, J, I, J, tuple(S.shape)))
         if tuple(C.shape) != (R, K):
             raise ValueError("C must be (%d, %d), got %s" % (R, K, tuple(C.shape)))
-        seed, replicate = int(seed), int(replicate)
-        if not -2 ** 63 <= seed < 2 ** 64:
-            raise ValueError("seed must fit 64 bits, got %r" % (seed,))
-        if not 0 <= replicate < 2 ** 31:
-            raise ValueError("replicate must be in [0, 2^31), got %r" % (replicate,))
-        return R, (seed - 2 ** 64 if seed >= 2 ** 63 else seed)
+        if not 0 <= int(replicate) < 2 ** 31:
+            raise ValueError("replicate must be in [0, 2^31), got %r" % (int(replicate),))
+        return R, _seed64(int(seed))
 
     def resample(self, S, C, seed=0, replicate=0):
         """New readings drawn from the model at (S, C) over the same sampling pattern: the draw of
@@ -483,8 +490,7 @@ class Observations:
     @staticmethod
     def check_select(K, I, J, pixels=None, bins=None, perm="keep"):
         """Host-side checks of select's arguments, before any device call: pixels an (I, J) bool
-        tensor or None, bins a (K,) bool tensor or None, perm "keep" or "fresh".  Raises
-        ValueError."""
+        tensor or None, bins a (K,) bool tensor or None, a perm.  Raises ValueError."""
         for name, t, shape in (("pixels", pixels, (I, J)), ("bins", bins, (K,))):
             if t is None:
                 continue
@@ -493,14 +499,12 @@ class Observations:
                                  % (name, t.dtype if isinstance(t, torch.Tensor) else type(t)))
             if tuple(t.shape) != shape:
                 raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-        if perm not in ("keep", "fresh"):
-            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+        _check_perm(perm)
 
     @staticmethod
     def check_split(frac=None, seed=0, n=None, perm="keep"):
         """Host-side checks of split's (frac) and folds' (n) arguments, before any device call:
-        0 < frac < 1, 2 <= n <= 65536, seed in [-2^63, 2^64) (resample's range), perm "keep" or
-        "fresh".  -> seed as a signed 64-bit value.  Raises ValueError."""
+        0 < frac < 1, 2 <= n <= 65536, int seed, perm.  -> _seed64(seed).  Raises ValueError."""
         if frac is not None:
             try:
                 ok = 0.0 < float(frac) < 1.0
@@ -511,13 +515,10 @@ class Observations:
         if n is not None:
             if isinstance(n, bool) or not isinstance(n, int) or not 2 <= n <= 65536:
                 raise ValueError("the number of folds must be an int in [2, 65536], got %r" % (n,))
+        _check_perm(perm)
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise ValueError("seed must be an int, got %r" % (seed,))
-        if not -2 ** 63 <= seed < 2 ** 64:
-            raise ValueError("seed must fit 64 bits, got %r" % (seed,))
-        if perm not in ("keep", "fresh"):
-            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
-        return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+        return _seed64(seed)
 
     def _child(self):
         """A new Observations with this one's shape, model, loss, tile, R_hint and schedule flag
@@ -691,8 +692,7 @@ class Observations:
         (before any device call), and with the number of readings out of range; nothing is
         built then."""
         K, I, J, m = self.check_readings(k, i, j, code, (self.K, self.I, self.J))
-        if perm not in ("keep", "fresh"):
-            raise ValueError('perm must be "keep" or "fresh", got %r' % (perm,))
+        _check_perm(perm)
         n, P = self.nnz, self.P
         if n + m >= 2 ** 31:
             raise ValueError("at most 2^31 - 1 readings are supported, got %d + %d" % (n, m))
